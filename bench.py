@@ -6,10 +6,17 @@ forward, guidance combine) + the DDIM update, exactly the body of ddim.py:206-22
 configs[1]: B = 4 per GPU, 8 s audio latent (4x16x64), 32 CAVP context frames, guidance 4.5, 16-bit MFMA operands (fp16
 headline -- the operand type that meets the north-star tolerance -- with the bf16 build timed beside it in `modes`),
 procedurally generated weights of the full 860 M-parameter UNet (no checkpoint is reachable offline).
-The engine is the PRODUCT's: no tuning call, plans from the shipped table of the GPU (diff_foley_amd/tuned/); `modes.untuned`
-times the cost-model plans in a child process, `sampler_loop` the same workload through LatentDiffusion.sample_log_diff_sampler.
+The engine is the PRODUCT's: no tuning call, plans from the shipped table of the GPU (diff_foley_amd/tuned/).
 
-    python bench.py --gpus 1 --steps 25 --warmup 3
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`, `dtype`, ...).
+Everything else moves behind --full: the instrumented per-kernel-family pass (`roofline`, `kernel_ms_per_step`,
+`north_star_families`, --dump-ops), `sampler_loop` (the same workload through LatentDiffusion.sample_log_diff_sampler),
+`vae_decode_roofline`, `batch8`, `config2_classifier_guided`, `modes` (the other operand type, the in-bench golden check and
+`modes.untuned`: the cost-model plans in a child process) and `cpu_baseline`; the --no-* switches trim that set.
+--dump-outputs DIR writes what the last timed step computed (latent, pred_x0, guided eps) as float32 .npy files; the inputs
+are seeded, so two builds run with the same arguments can be compared output for output.
+
+    python bench.py --gpus 1 --steps 25 --warmup 3 [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 """
@@ -167,11 +174,14 @@ def run_mode(precision, sd_dev, a, dev, rank, world, lo, hi, barrier, dump_ops="
     if hoist:
         eng.set_timesteps([float(v) for v in steps], B, 16, 64, True)
 
+    last = {}       # the last step's other results (fresh tensors every step), for --dump-outputs
+
     def step(i, x):
         i = i % 25
         idx = 25 - i - 1
         e = eng.unet_forward_cfg(x, t_all[i], 4.5, ts_index=i if hoist else None)
-        xn, _ = E.ddim_update(x, e, tb.alphas[idx], tb.alphas_prev[idx], 0.0, tb.sqrt_one_minus_alphas[idx])
+        xn, p0 = E.ddim_update(x, e, tb.alphas[idx], tb.alphas_prev[idx], 0.0, tb.sqrt_one_minus_alphas[idx])
+        last["pred_x0"], last["eps"] = p0, e
         return xn
 
     for i in range(a.warmup):
@@ -189,6 +199,10 @@ def run_mode(precision, sd_dev, a, dev, rank, world, lo, hi, barrier, dump_ops="
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
     assert torch.isfinite(x).all() or os.environ.get("DF_GEMM_DBG")
+    outputs = {"latent": x, "pred_x0": last["pred_x0"], "eps": last["eps"]}
+    if not a.full:
+        return dict(model=model, dt=dt, outputs=outputs, stats=eng.plan_stats(), t_setup=t_setup,
+                    dist=gather_dist_info(dist_info, dev, rank, world), plan_source=plan_source_of(a, eng))
 
     # ---- per-kernel-family time: HIP events on the launch stream around every op of the same K steps (second,
     # instrumented pass; the events themselves cost ~2 us per op, so the family times are NORMALISED to the
@@ -234,25 +248,46 @@ def run_mode(precision, sd_dev, a, dev, rank, world, lo, hi, barrier, dump_ops="
         dl = time.perf_counter() - t1
         loop = {"steps": 25 * ncall, "steps_per_s": round(25 * ncall / dl, 3), "ms_per_step": round(dl / (25 * ncall) * 1e3, 4),
                 "what": "LatentDiffusion.sample_log_diff_sampler('DDIM', 25 steps, CFG 4.5) x 4 calls incl. set_context per call"}
-    if world > 1:       # every rank's pack / broadcast / import seconds in the one JSON line (first real SCALE run shows them)
-        infos = [None] * world
-        # what each rank saw of the job: the world size of its process group on its backend ("nccl" = RCCL), the device it
-        # computes on and that device's PCI bus id -- a SCALE run with two ranks on one GPU, or a rank that fell back to gloo,
-        # shows in the line itself
-        try:
-            bus = torch.cuda.get_device_properties(dev).pci_bus_id
-        except Exception:
-            bus = None
-        seen = dict(rccl_world_seen=torch.distributed.get_world_size(), pg_backend=torch.distributed.get_backend(),
-                    cuda_device=torch.cuda.current_device(), pci_bus_id=bus, gpu_name=torch.cuda.get_device_name(dev))
-        torch.distributed.all_gather_object(infos, dict(rank=rank, **seen, **{k: (round(v, 4) if isinstance(v, float) else v)
-                                                                             for k, v in (dist_info or {}).items()}))
-        dist_info = {"per_rank": infos}
-    plan_source = ("autotuned in this process (--autotune)" if a.autotune else
-                   (f"shipped table {os.path.relpath(eng.tuned_defaults, ROOT)}" if eng.tuned_defaults else
-                    "cost-model tiles (DF_TUNED_DEFAULTS=0 or no table for this device)"))
-    return dict(model=model, dt=dt, prof=prof, sub=sub, stats=eng.plan_stats(), t_setup=t_setup, dist=dist_info, loop=loop,
-                plan_source=plan_source)
+    return dict(model=model, dt=dt, outputs=outputs, prof=prof, sub=sub, stats=eng.plan_stats(), t_setup=t_setup,
+                dist=gather_dist_info(dist_info, dev, rank, world), loop=loop, plan_source=plan_source_of(a, eng))
+
+
+def gather_dist_info(dist_info, dev, rank, world):
+    """N > 1: every rank's pack / broadcast / import seconds in the one JSON line (first real SCALE run shows them)."""
+    if world == 1:
+        return dist_info
+    infos = [None] * world
+    # what each rank saw of the job: the world size of its process group on its backend ("nccl" = RCCL), the device it
+    # computes on and that device's PCI bus id -- a SCALE run with two ranks on one GPU, or a rank that fell back to gloo,
+    # shows in the line itself
+    try:
+        bus = torch.cuda.get_device_properties(dev).pci_bus_id
+    except Exception:
+        bus = None
+    seen = dict(rccl_world_seen=torch.distributed.get_world_size(), pg_backend=torch.distributed.get_backend(),
+                cuda_device=torch.cuda.current_device(), pci_bus_id=bus, gpu_name=torch.cuda.get_device_name(dev))
+    torch.distributed.all_gather_object(infos, dict(rank=rank, **seen, **{k: (round(v, 4) if isinstance(v, float) else v)
+                                                                         for k, v in (dist_info or {}).items()}))
+    return {"per_rank": infos}
+
+
+def plan_source_of(a, eng):
+    return ("autotuned in this process (--autotune)" if a.autotune else
+            (f"shipped table {os.path.relpath(eng.tuned_defaults, ROOT)}" if eng.tuned_defaults else
+             "cost-model tiles (DF_TUNED_DEFAULTS=0 or no table for this device)"))
+
+
+def dump_outputs(outputs, path, rank, world):
+    """--dump-outputs: the last timed step's results as float32 .npy files, every rank's shard in global sample order."""
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in outputs.items()}
+    if world > 1:
+        shards = [None] * world
+        torch.distributed.all_gather_object(shards, arrays)
+        arrays = {k: np.concatenate([s[k] for s in shards]) for k in arrays}
+    if rank == 0:
+        os.makedirs(path, exist_ok=True)
+        for k, v in arrays.items():
+            np.save(os.path.join(path, k + ".npy"), v.astype(np.float32))
 
 
 def batch8_block(model, dev, steps, warmup):
@@ -333,13 +368,13 @@ def config2_block(model, dev):
 
 def untuned_child(a):
     """`modes.untuned`: the same command in a child process with DF_TUNED_DEFAULTS=0 (the shipped table is imported once per
-    process and library, so the cost-model plans need a fresh process): headline loop only."""
+    process and library, so the cost-model plans need a fresh process): headline loop, instrumented pass and sampler loop."""
     import subprocess
     env = dict(os.environ, DF_TUNED_DEFAULTS="0")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "GROUP_RANK", "LOCAL_WORLD_SIZE", "TORCHELASTIC_RUN_ID"):
         env.pop(k, None)          # a plain single-process child even when this process was started by torch.distributed.run
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(a.steps), "--warmup", str(a.warmup), "--batch",
-           str(a.batch), "--precision", a.precision, "--no-cpu-baseline", "--no-modes", "--no-vae", "--no-batch8"]
+           str(a.batch), "--precision", a.precision, "--full", "--no-cpu-baseline", "--no-modes", "--no-vae", "--no-batch8"]
     try:
         r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=420)
         line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -406,10 +441,19 @@ def main():
                     help="MFMA operand type of the headline value.  fp16 (libdfengine_f16.so) is the default: same MFMA rate and "
                          "the operand type that meets the north-star bound (mel MAE < 1e-3 absolute); bf16 = the literal "
                          "wording of BASELINE configs[1], reported beside it in `modes` (mel MAE 4e-3)")
-    ap.add_argument("--dump-ops", default="", help="write a per-op CSV of the instrumented pass")
+    ap.add_argument("--dump-ops", default="", help="write a per-op CSV of the instrumented pass (--full)")
     ap.add_argument("--no-time-hoist", action="store_true",
                     help="compute the time embedding inside every step (4 launches) instead of once per sample() call")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the instrumented per-family pass (roofline, kernel times), sampler_loop, "
+                         "vae_decode_roofline, batch8, config2_classifier_guided, modes and cpu_baseline (--no-* trim the set)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's latent, pred_x0 and guided eps (every rank's shard) to DIR/<name>.npy, float32")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_ops and not a.full:
+        ap.error("--dump-ops writes the per-op CSV of the instrumented pass, which runs under --full")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: start the N ranks ourselves (one process per GPU, torch.distributed.run on a free
@@ -435,18 +479,14 @@ def main():
 
     lo, hi = parallel.shard_range(G, rank, world)
     main_run = run_mode(a.precision, sd_dev, a, dev, rank, world, lo, hi, barrier, a.dump_ops)
-    dt, prof, sub, stats = main_run["dt"], main_run["prof"], main_run["sub"], main_run["stats"]
+    dt, stats = main_run["dt"], main_run["stats"]
+    if a.dump_outputs:
+        dump_outputs(main_run["outputs"], a.dump_outputs, rank, world)
 
     if rank == 0:
         ms_step = dt / a.steps * 1e3
         per_gpu = a.steps / dt
         N = 2 * B
-        inst_total = sum(v["ms"] for v in prof.values()) / a.steps            # instrumented: includes event overhead
-        norm = ms_step / inst_total                                          # -> family times that sum to ms_per_step
-        fam_ms = {k: v["ms"] / a.steps * norm for k, v in prof.items()}
-        gemm_ms = fam_ms["gemm"]
-        gemm_launches = prof["gemm"]["launches"] // a.steps
-        gemm_tflops = GEMM_GFLOP_PER_SAMPLE * N / gemm_ms            # GFLOP / ms = TFLOP/s
         name = {"bf16": "bf16", "fp16": "f16"}
         out = {
             "metric": "UNet denoise steps/sec (8s audio latent, 25-step DDIM, CFG 4.5), aggregate over GPUs",
@@ -468,46 +508,56 @@ def main():
                        "weight_distribution": main_run["dist"],
                        "engine_setup_s": round(main_run["t_setup"], 3)},
             "step_tflops_algorithmic": round(GFLOP_PER_SAMPLE * N / ms_step, 2),
-            "roofline": {"bound": "mfma", "kernel": "gemm_bf16_kernel / conv3x3_halo_kernel (implicit-GEMM conv3x3/1x1/linear, all tile shapes, incl. split-K reduce)",
-                         "achieved": round(gemm_tflops, 2), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
-                         "frac": round(gemm_tflops / PEAK_BF16_TFLOPS, 4),
-                         "launches_per_step": int(gemm_launches), "avg_launch_us": round(gemm_ms * 1e3 / max(1, gemm_launches), 2),
-                         "algorithmic_gflop_per_step": round(GEMM_GFLOP_PER_SAMPLE * N, 1),
-                         "family_ms_per_step": round(gemm_ms, 4),
-                         "time_source": "HIP events around every op of the K steps on the launch stream, normalised so that the "
-                                        "families sum to the un-instrumented ms_per_step (events add ~2 us per op)",
-                         "traffic": pmc_traffic("gemm_bytes_per_step"), "traffic_unit": "HBM-side bytes per STEP of this kernel family (2 x FETCH_SIZE + WRITE_SIZE)",
-                         "traffic_per_launch": pmc_traffic("gemm_bytes_per_launch"),
-                         "algorithmic_bytes_per_step": round((1.7186 + 0.4478 * B) * 1e9),
-                         "traffic_source": "profiles/pmc_traffic.json (rocprofv3 --pmc passes of this command; not measured in this run)",
-                         "peak_measured": measured_peak(), "peak_measured_source": "profiles/peaks.json (tools/peaks.py on an MI355X; not measured in this run)",
-                         "mfma_busy_pmc": sq_counters(), "mfma_busy_pmc_source": "profiles/sq_counters.json (SQ_VALU_MFMA_BUSY_CYCLES / (32 x SQ_BUSY_CYCLES) per kernel "
-                                                                              "family over 4 denoise steps of this command; includes the matrix pipe's time on padded tiles, "
-                                                                              "so it sits above the algorithmic frac; not measured in this run)"},
-            "north_star_families": None if not sub else {
-                "spatial_transformer": {"algorithmic_gflop_per_step": round(73.22 * N, 1), "ms_per_step": round(sub["st_ms"] * norm, 4),
-                                        "launches_per_step": sub["st_launches"],
-                                        "tflops": round(73.22 * N / (sub["st_ms"] * norm), 1),
-                                        "frac_of_mfma_peak": round(73.22 * N / (sub["st_ms"] * norm) / PEAK_BF16_TFLOPS, 4)},
-                "resblock_conv3x3": {"algorithmic_gb_per_step": round(1.0235 + 0.0403 * N, 4), "ms_per_step": round(sub["rc_ms"] * norm, 4),
-                                     "gb_per_s": round((1.0235 + 0.0403 * N) / (sub["rc_ms"] * norm) * 1e3, 1),
-                                     "frac_of_hbm_peak": round((1.0235 + 0.0403 * N) / (sub["rc_ms"] * norm) * 1e3 / 8000.0, 4),
-                                     "tflops": round(81.62 * N / (sub["rc_ms"] * norm), 1)}},
-            "sampler_loop": main_run["loop"],
-            "kernel_ms_per_step": {k: round(v, 4) for k, v in fam_ms.items()},
-            "kernel_ms_per_step_instrumented": {k: round(v["ms"] / a.steps, 4) for k, v in prof.items()},
-            "kernel_launches_per_step": {k: int(v["launches"] // a.steps) for k, v in prof.items()},
-            "plan": stats,
         }
-        if world == 1 and not a.no_vae:
+        if a.full:
+            prof, sub = main_run["prof"], main_run["sub"]
+            inst_total = sum(v["ms"] for v in prof.values()) / a.steps            # instrumented: includes event overhead
+            norm = ms_step / inst_total                                          # -> family times that sum to ms_per_step
+            fam_ms = {k: v["ms"] / a.steps * norm for k, v in prof.items()}
+            gemm_ms = fam_ms["gemm"]
+            gemm_launches = prof["gemm"]["launches"] // a.steps
+            gemm_tflops = GEMM_GFLOP_PER_SAMPLE * N / gemm_ms            # GFLOP / ms = TFLOP/s
+            out.update({
+                "roofline": {"bound": "mfma", "kernel": "gemm_bf16_kernel / conv3x3_halo_kernel (implicit-GEMM conv3x3/1x1/linear, all tile shapes, incl. split-K reduce)",
+                             "achieved": round(gemm_tflops, 2), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
+                             "frac": round(gemm_tflops / PEAK_BF16_TFLOPS, 4),
+                             "launches_per_step": int(gemm_launches), "avg_launch_us": round(gemm_ms * 1e3 / max(1, gemm_launches), 2),
+                             "algorithmic_gflop_per_step": round(GEMM_GFLOP_PER_SAMPLE * N, 1),
+                             "family_ms_per_step": round(gemm_ms, 4),
+                             "time_source": "HIP events around every op of the K steps on the launch stream, normalised so that the "
+                                            "families sum to the un-instrumented ms_per_step (events add ~2 us per op)",
+                             "traffic": pmc_traffic("gemm_bytes_per_step"), "traffic_unit": "HBM-side bytes per STEP of this kernel family (2 x FETCH_SIZE + WRITE_SIZE)",
+                             "traffic_per_launch": pmc_traffic("gemm_bytes_per_launch"),
+                             "algorithmic_bytes_per_step": round((1.7186 + 0.4478 * B) * 1e9),
+                             "traffic_source": "profiles/pmc_traffic.json (rocprofv3 --pmc passes of this command; not measured in this run)",
+                             "peak_measured": measured_peak(), "peak_measured_source": "profiles/peaks.json (tools/peaks.py on an MI355X; not measured in this run)",
+                             "mfma_busy_pmc": sq_counters(), "mfma_busy_pmc_source": "profiles/sq_counters.json (SQ_VALU_MFMA_BUSY_CYCLES / (32 x SQ_BUSY_CYCLES) per kernel "
+                                                                                  "family over 4 denoise steps of this command; includes the matrix pipe's time on padded tiles, "
+                                                                                  "so it sits above the algorithmic frac; not measured in this run)"},
+                "north_star_families": None if not sub else {
+                    "spatial_transformer": {"algorithmic_gflop_per_step": round(73.22 * N, 1), "ms_per_step": round(sub["st_ms"] * norm, 4),
+                                            "launches_per_step": sub["st_launches"],
+                                            "tflops": round(73.22 * N / (sub["st_ms"] * norm), 1),
+                                            "frac_of_mfma_peak": round(73.22 * N / (sub["st_ms"] * norm) / PEAK_BF16_TFLOPS, 4)},
+                    "resblock_conv3x3": {"algorithmic_gb_per_step": round(1.0235 + 0.0403 * N, 4), "ms_per_step": round(sub["rc_ms"] * norm, 4),
+                                         "gb_per_s": round((1.0235 + 0.0403 * N) / (sub["rc_ms"] * norm) * 1e3, 1),
+                                         "frac_of_hbm_peak": round((1.0235 + 0.0403 * N) / (sub["rc_ms"] * norm) * 1e3 / 8000.0, 4),
+                                         "tflops": round(81.62 * N / (sub["rc_ms"] * norm), 1)}},
+                "sampler_loop": main_run["loop"],
+                "kernel_ms_per_step": {k: round(v, 4) for k, v in fam_ms.items()},
+                "kernel_ms_per_step_instrumented": {k: round(v["ms"] / a.steps, 4) for k, v in prof.items()},
+                "kernel_launches_per_step": {k: int(v["launches"] // a.steps) for k, v in prof.items()},
+            })
+        out["plan"] = stats
+        if a.full and world == 1 and not a.no_vae:
             out["vae_decode_roofline"] = vae_roofline(main_run["model"], dev, B)
-        if world == 1 and not a.no_batch8:
+        if a.full and world == 1 and not a.no_batch8:
             out["batch8"] = batch8_block(main_run["model"], dev, max(10, a.steps // 2), a.warmup)
             try:
                 out["config2_classifier_guided"] = config2_block(main_run["model"], dev)
             except Exception as ex:      # must not hide the headline number
                 out["config2_classifier_guided"] = {"error": f"{type(ex).__name__}: {ex}"}
-        if world == 1 and not a.no_modes:
+        if a.full and world == 1 and not a.no_modes:
             # both MFMA operand types in ONE driver-run line: steps/s of the same workload + the north-star parity metric
             # (mel MAE of a 25-step DDIM sample against the reference's golden output) measured in this very process
             modes = {}
@@ -526,7 +576,7 @@ def main():
             out["parity_target"] = "north_star: mel-spec MAE < 1e-3 vs the CPU reference (absolute, mel units); " \
                                    "golden = tests/golden/g5_full_samplers.npz (reference output, B=1, seed 21)"
         del main_run
-        if not a.no_cpu_baseline and world == 1:       # reported at N=1 only (rank 0's host cores)
+        if a.full and not a.no_cpu_baseline and world == 1:       # reported at N=1 only (rank 0's host cores)
             out["cpu_baseline"] = cpu_baseline(sd, a.cpu_steps)
         print(json.dumps(out))
     if world > 1:

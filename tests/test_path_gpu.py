@@ -1027,7 +1027,7 @@ def test_shipped_plan_is_reproducible_run_to_run(prec):
     assert d["diverged"] == 0 and d["nonfinite_outputs"] == 0, d
 
 
-def test_facade_runs_the_shipped_plan_table(P):
+def test_facade_runs_the_shipped_plan_table(P, tmp_path):
     """The drop-in never calls a tuning step (inference/diff_foley_inference.ipynb:80-95 has none): LatentDiffusion(...).cuda()
     imports the shipped table of this GPU model (diff_foley_amd/tuned/, engine.load_tuned_defaults) and every GEMM of the
     BASELINE configs[1] step then runs the (tile, split-K) the table holds for its shape -- the kernels bench.py times."""
@@ -1053,7 +1053,7 @@ def test_facade_runs_the_shipped_plan_table(P):
     eng.profile_begin()
     z, _ = m.sample_log_diff_sampler(c, B, "DDIM", 2, unconditional_guidance_scale=4.5, unconditional_conditioning=torch.zeros_like(c), x_T=xT)
     eng.profile_end()
-    path = "/tmp/df_shipped_plan_ops.csv"
+    path = str(tmp_path / "df_shipped_plan_ops.csv")
     eng.profile_dump(path)
     rows = [r for r in csv.DictReader(open(path)) if int(r["K"]) > 0 and r["tag"] != "out.conv"]
     assert len(rows) > 200
@@ -1066,7 +1066,7 @@ def test_facade_runs_the_shipped_plan_table(P):
     assert any(int(r["tile"]) >= 18 for r in rows)
 
 
-def test_batch_outside_the_shipped_table_takes_its_nearest_entries(full):
+def test_batch_outside_the_shipped_table_takes_its_nearest_entries(full, tmp_path):
     """A sampler batch the shipped table does not hold (B = 10: UNet batch 20) builds its plan from the entries of the nearest row
     count (engine.hip nearest_tune_choice: another batch size changes M only), not from the cost model -- the plan carries the
     producer-specialised / wide tiles -- and, samples being independent, its row 0 equals the B = 1 run to operand-rounding noise."""
@@ -1084,8 +1084,9 @@ def test_batch_outside_the_shipped_table_takes_its_nearest_entries(full):
     eng.profile_begin()
     full.sample_log_diff_sampler(c, B, "DDIM", 1 + 1, unconditional_guidance_scale=4.5, unconditional_conditioning=uc, x_T=xT.clone())
     eng.profile_end()
-    eng.profile_dump("/tmp/df_b10_ops.csv")
-    rows = [r for r in csv.DictReader(open("/tmp/df_b10_ops.csv")) if int(r["K"]) > 0]
+    path = str(tmp_path / "df_b10_ops.csv")
+    eng.profile_dump(path)
+    rows = [r for r in csv.DictReader(open(path)) if int(r["K"]) > 0]
     table_m = {int(line.split("_")[0]) for line in open(eng.tuned_defaults)}
     assert any(int(r["M"]) not in table_m for r in rows)                      # the shape class really is outside the table
     ff1 = [r for r in rows if r["tag"] == "st.ff1"]

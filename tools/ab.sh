@@ -4,7 +4,7 @@
 for pass in 1 2; do
   for arm in "$@"; do
     label=${arm%%|*}; envs=${arm#*|}
-    env $envs python bench.py --no-cpu-baseline 2>/dev/null | tail -1 > /tmp/_ab.json
+    env $envs python bench.py --full --no-cpu-baseline 2>/dev/null | tail -1 > /tmp/_ab.json
     python - "$label" "$pass" <<'PY'
 import json,sys
 d=json.load(open('/tmp/_ab.json'))

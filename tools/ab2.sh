@@ -3,7 +3,7 @@
 for pass in 1 2; do
   for arm in "$@"; do
     label=${arm%%|*}; envs=${arm#*|}
-    env $envs python bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-modes --no-vae --no-time-hoist 2>/dev/null | tail -1 > /tmp/_ab.json
+    env $envs python bench.py --steps 40 --warmup 5 --full --no-cpu-baseline --no-modes --no-vae --no-time-hoist 2>/dev/null | tail -1 > /tmp/_ab.json
     python - "$label" "$pass" <<'PY'
 import json,sys
 d=json.load(open('/tmp/_ab.json'))

@@ -3,9 +3,9 @@
 ROOTD=$(pwd); label=$1; shift
 OUT=$ROOTD/gpurun_out/prof_$label; mkdir -p $OUT
 export DF_TUNE_CACHE=$OUT/tune.txt
-env "$@" python bench.py --no-cpu-baseline > $OUT/bench.json 2>/dev/null
+env "$@" python bench.py --full --no-cpu-baseline > $OUT/bench.json 2>/dev/null
 cd /tmp && export TMPDIR=/tmp
-env "$@" rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o s -- python $ROOTD/bench.py --steps 25 --no-cpu-baseline > $OUT/rocprof_bench.json 2>/dev/null
+env "$@" rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o s -- python $ROOTD/bench.py --steps 25 --full --no-cpu-baseline > $OUT/rocprof_bench.json 2>/dev/null
 cd $ROOTD
 find $OUT/stats -name "*kernel_stats.csv" -exec cp {} $OUT/kernel_stats.csv \;
 find $OUT/stats -name "*kernel_trace.csv" -exec cp {} $OUT/kernel_trace.csv \;

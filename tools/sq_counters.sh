@@ -7,7 +7,7 @@ OUT=${1:-$ROOTD/gpurun_out/sq}
 case $OUT in /*) ;; *) OUT=$ROOTD/$OUT ;; esac
 rm -rf $OUT; mkdir -p $OUT
 # (round 6: bench.py runs the shipped plan table -- no tuning pass, rocprof sees product launches only; DF_TUNE_CACHE no longer needed)
-ARGS="--steps 5 --warmup 2 --no-cpu-baseline --no-modes --no-vae --no-batch8"
+ARGS="--steps 5 --warmup 2 --full --no-cpu-baseline --no-modes --no-vae --no-batch8"
 python bench.py $ARGS 2>/dev/null | tail -1 | cut -c1-160
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --pmc SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES \
