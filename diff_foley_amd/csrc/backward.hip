@@ -603,8 +603,9 @@ __global__ __launch_bounds__(512) void attention_bwd_mfma_kernel(const bf16_t* _
 
 // ------------------------------------------------------------------ classifier head backward
 // p = sigmoid(z), objective sum log p  ->  dz = 1 - p;  pooled = mean_px(h);  z = w . pooled + b
-//   dh[n][px][c] = (1 - p_n) * w[c] / HW          (out_channels == 1)
+//   dh[n][px][c] = dz_n * w[c] / HW          (out_channels == 1)
 //   dh_b16: the same values as the next conv's gradient operand, rows of Cp >= C columns, the pad columns zero
+// prob == nullptr: dz = 1 (the gradient plan runs the VJP of z and applies 1 - p_n at the end, grad_scale_per_sample_kernel)
 __global__ void cls_head_bwd_kernel(const float* __restrict__ prob, const float* __restrict__ w, float* __restrict__ dh,
                                     bf16_t* __restrict__ dh_b16, int N, int HW, int C, int Cp) {
   const long total = (long)N * HW * Cp;
@@ -613,13 +614,22 @@ __global__ void cls_head_bwd_kernel(const float* __restrict__ prob, const float*
     const long row = i / Cp;
     const int n = (int)(row / HW);
     if (c < C) {
-      const float v = (1.0f - prob[n]) * w[c] / (float)HW;
+      const float v = (prob ? 1.0f - prob[n] : 1.0f) * w[c] / (float)HW;
       dh[row * C + c] = v;
       if (dh_b16) dh_b16[i] = f2bf(v);
     } else if (dh_b16) {
       dh_b16[i] = (bf16_t)0;
     }
   }
+}
+
+// x[n][..] *= 1 - prob[n] over `per` values per sample, in fp32: the classifier gradient's last step.  The backward pass itself runs
+// on the logit's cotangent 1: with 1 - p_n folded into the head's cotangent, a confident sample (p -> 1) put every fp16 gradient
+// operand behind it into the subnormal range (1e-4 * w / HW ~ 1e-7 < 6.1e-5).
+__global__ void grad_scale_per_sample_kernel(float* __restrict__ x, const float* __restrict__ prob, long per, int N) {
+  const long total = (long)N * per;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x)
+    x[i] *= 1.0f - prob[i / per];
 }
 
 // Linear weight [O][I] fp32 -> transposed bf16 [I][O]
@@ -700,25 +710,34 @@ size_t attention_bwd_ws_floats(int N, int heads, int D, int Tq, int Tk, int lddk
 hipError_t launch_attention_bwd(const uint16_t* Q, int ldq, const uint16_t* K, int ldk, const uint16_t* Vt, int ldvt,
                                 const float* dO, int lddo, uint16_t* dQ, int lddq, uint16_t* dK, int lddk, uint16_t* dV,
                                 int lddv, int N, int heads, int D, int Tq, int Tk, float scale, float* ws, hipStream_t s) {
+  return launch_attention_bwd(Q, ldq, K, ldk, Vt, ldvt, dO, lddo, dQ, lddq, dK, lddk, dV, lddv, N, heads, D, Tq, Tk, scale, ws, -1, s);
+}
+
+hipError_t launch_attention_bwd(const uint16_t* Q, int ldq, const uint16_t* K, int ldk, const uint16_t* Vt, int ldvt,
+                                const float* dO, int lddo, uint16_t* dQ, int lddq, uint16_t* dK, int lddk, uint16_t* dV,
+                                int lddv, int N, int heads, int D, int Tq, int Tk, float scale, float* ws, int form, hipStream_t s) {
   if (D != 32 && D != 64) return hipErrorInvalidValue;
-  {
-    const int nkt = (Tk + 31) / 32;
-    const size_t ldm = attn_bwd_mfma_lds(D, Tq, Tk, lddk, lddv);
-    if (ldm) {
-      static size_t attr_m = 0;
-      if (ldm > attr_m) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_bwd_mfma_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldm);
-        if (e != hipSuccess) return e;
-        attr_m = ldm;
-      }
-      hipLaunchKernelGGL(attention_bwd_mfma_kernel, dim3(heads, N), dim3(64 * nkt), ldm, s, Q, ldq, K, ldk, Vt, ldvt, dO,
-                         lddo, dQ, lddq, dK, lddk, dV, lddv, heads, Tq, Tk, scale);
-      return hipGetLastError();
-    }
-  }
+  if (form < -1 || form > 2) return hipErrorInvalidValue;
+  // form -1: the first form that takes the shape, in the order MFMA, VALU resident, tiled pair; a forced form that does not
+  // take the shape is an error, never another form
+  const size_t ldm = attn_bwd_mfma_lds(D, Tq, Tk, lddk, lddv);
   const size_t lds = attn_bwd_valu_lds(D, Tq, Tk);
-  if (!lds) {      // no resident form: the tiled pair (row statistics through `ws`)
+  if (form == -1) form = ldm ? 0 : (lds ? 1 : 2);
+  if ((form == 0 && !ldm) || (form == 1 && !lds)) return hipErrorInvalidValue;
+  if (form == 0) {
+    const int nkt = (Tk + 31) / 32;
+    static size_t attr_m = 0;
+    if (ldm > attr_m) {
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_bwd_mfma_kernel),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldm);
+      if (e != hipSuccess) return e;
+      attr_m = ldm;
+    }
+    hipLaunchKernelGGL(attention_bwd_mfma_kernel, dim3(heads, N), dim3(64 * nkt), ldm, s, Q, ldq, K, ldk, Vt, ldvt, dO,
+                       lddo, dQ, lddq, dK, lddk, dV, lddv, heads, Tq, Tk, scale);
+    return hipGetLastError();
+  }
+  if (form == 2) {      // no resident form: the tiled pair (row statistics through `ws`)
     if (dK && !ws) return hipErrorInvalidValue;
     const dim3 gq((Tq + 63) / 64, heads, N), gk((Tk + 63) / 64, heads, N);
 #define DF_ABWD_T(DD)                                                                                                             \
@@ -757,6 +776,11 @@ hipError_t launch_cls_head_bwd(const float* prob, const float* w, float* dh, uin
                                hipStream_t s) {
   if (Cp < C) return hipErrorInvalidValue;
   hipLaunchKernelGGL(cls_head_bwd_kernel, dim3(grid_for((long)N * HW * Cp)), dim3(256), 0, s, prob, w, dh, dh_b16, N, HW, C, Cp);
+  return hipGetLastError();
+}
+
+hipError_t launch_grad_scale_per_sample(float* x, const float* prob, int N, long per, hipStream_t s) {
+  hipLaunchKernelGGL(grad_scale_per_sample_kernel, dim3(grid_for((long)N * per)), dim3(256), 0, s, x, prob, per, N);
   return hipGetLastError();
 }
 

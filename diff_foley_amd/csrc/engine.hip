@@ -2011,11 +2011,15 @@ void build_classifier_grad(df_ctx* c, Plan* pl, int N, int H, int W, int Tc) {
   {
     const float* wcls = c->f32(pre + "classifier.weight");
     float* dp = dho.p;
-    b.other("cls.head.bwd", [=](hipStream_t s, const RunArgs&) { return launch_cls_head_bwd(prob, wcls, dp, dhob, N, hw2, co, cop, s); });
+    // the VJP of the logit (cotangent 1); 1 - p_n is applied to the finished gradient in fp32 (cls.grad.scale): folded into the
+    // cotangent here it took a confident sample's fp16 gradient operands into the subnormal range
+    b.other("cls.head.bwd", [=](hipStream_t s, const RunArgs&) { return launch_cls_head_bwd(nullptr, wcls, dp, dhob, N, hw2, co, cop, s); });
   }
   F32 d_ah = conv_bwd(dhob, hm, wmid, cop, pre + "out.2.weight", chf, "cls.out.bwd");
   F32 g = gn_bwd(h, "out.0", 1e-5f, 1, d_ah, nullptr, true, nullptr);
   for (int i = (int)tape.size() - 1; i >= 0; --i) g = tape[i](g);
+  const long per = (long)cin * HW;
+  b.other("cls.grad.scale", [=](hipStream_t s, const RunArgs& a) { return launch_grad_scale_per_sample(a.out, prob, N, per, s); });
 }
 
 // VAE decoder plan (autoencoder.py:330-333, stage1_autoencoder/model.py:630-663)
@@ -3246,11 +3250,19 @@ int df_vae_decode(df_ctx* c, const float* z, float* out, int B, int H, int W, vo
   });
 }
 
+// The engine sizes every Downsample output as floor(H / 2) x floor(W / 2) where torch's stride-2 conv gives the ceiling, and its
+// backward has no odd-size transposed conv: a map that does not survive the downsampling is refused, as unet_plan does.
+static void cls_need_divisible(df_ctx* c, int H, int W) {
+  const int ds = 1 << (c->ccfg.n_mult - 1);
+  if (H % ds || W % ds) fail("classifier: latent %dx%d not divisible by the classifier's downsampling (%d)", H, W, ds);
+}
+
 int df_classifier_forward(df_ctx* c, const float* x, const float* t, const float* feat, float* prob, int B, int H,
                           int W, int T, void* stream) {
   return guard([&] {
     if (!c->has_cls) fail("classifier not configured");
     need_positive("classifier", {{"batch", B}, {"H", H}, {"W", W}, {"video frames", T}});
+    cls_need_divisible(c, H, W);
     Plan* p = get_plan(c, keyf("cls_%d_%d_%d_%d", B, H, W, T),
                        [&](Plan* pl) { build_unet_like(c, pl, 1, B, H, W, T, false, true); });
     RunArgs a;
@@ -3267,6 +3279,7 @@ int df_classifier_grad_cached(df_ctx* c, const float* x, const float* t, const f
   return guard([&] {
     if (!c->has_cls) fail("classifier not configured");
     need_positive("classifier gradient", {{"batch", B}, {"H", H}, {"W", W}, {"video frames", T}});
+    cls_need_divisible(c, H, W);
     Plan* p = get_plan(c, keyf("clsgrad_%d_%d_%d_%d", B, H, W, T), [&](Plan* pl) { build_classifier_grad(c, pl, B, H, W, T); });
     RunArgs a;
     a.x = x;
@@ -3929,6 +3942,70 @@ int df_test_layernorm(const float* x, int rows, int C, const float* gamma, const
 int df_test_attention(const uint16_t* Q, int ldq, const uint16_t* K, int ldk, const uint16_t* Vt, int ldvt, uint16_t* O,
                       int ldo, int N, int heads, int D, int Tq, int Tk, float scale, void* stream) {
   return guard([&] { HIPCHK(launch_attention(Q, ldq, K, ldk, Vt, ldvt, O, ldo, N, heads, D, Tq, Tk, scale, (hipStream_t)stream)); });
+}
+
+// ---- the classifier's input-gradient kernels (csrc/backward.hip) one at a time
+int df_test_groupnorm_bwd(const float* x, int ld, int N, int HW, int C, const float* gamma, const float* beta, float eps, int silu,
+                          const float* dy, int lddy, const float* addend, int ldadd, float* dx, int lddx, uint16_t* dx_b16,
+                          void* stream) {
+  return guard([&] {
+    HIPCHK(launch_groupnorm_bwd(x, ld, N, HW, C, gamma, beta, eps, silu, dy, lddy, addend, ldadd, dx, lddx, dx_b16,
+                                (hipStream_t)stream));
+  });
+}
+int df_test_layernorm_bwd(const float* x, int rows, int C, const float* gamma, float eps, const float* dy, const float* addend,
+                          float* dx, uint16_t* dx_b16, void* stream) {
+  return guard([&] { HIPCHK(launch_layernorm_bwd(x, rows, C, gamma, eps, dy, addend, dx, dx_b16, (hipStream_t)stream)); });
+}
+int df_test_geglu_fwd(const uint16_t* u, uint16_t* y, int64_t rows, int H, void* stream) {
+  return guard([&] { HIPCHK(launch_geglu_fwd(u, y, (long)rows, H, (hipStream_t)stream)); });
+}
+int df_test_geglu_bwd(const uint16_t* u, const float* dy, uint16_t* du, int64_t rows, int H, void* stream) {
+  return guard([&] { HIPCHK(launch_geglu_bwd(u, dy, du, (long)rows, H, (hipStream_t)stream)); });
+}
+int df_test_attention_bwd(const uint16_t* Q, int ldq, const uint16_t* K, int ldk, const uint16_t* Vt, int ldvt, const float* dO,
+                          int lddo, uint16_t* dQ, int lddq, uint16_t* dK, int lddk, uint16_t* dV, int lddv, int N, int heads, int D,
+                          int Tq, int Tk, float scale, int form, void* stream) {
+  return guard([&] {
+    size_t nws = attention_bwd_ws_floats(N, heads, D, Tq, Tk, lddk, lddv, dK != nullptr);
+    if (form == 2 && dK) nws = (size_t)N * heads * Tq * 3;      // the tiled pair forced on a shape a resident form would take
+    float* ws = nws ? test_partial(nws * 4) : nullptr;
+    HIPCHK(launch_attention_bwd(Q, ldq, K, ldk, Vt, ldvt, dO, lddo, dQ, lddq, dK, lddk, dV, lddv, N, heads, D, Tq, Tk, scale, ws,
+                                form, (hipStream_t)stream));
+  });
+}
+int df_test_cls_head_bwd(const float* prob, const float* w, float* dh, uint16_t* dh_b16, int N, int HW, int C, int Cp, void* stream) {
+  return guard([&] { HIPCHK(launch_cls_head_bwd(prob, w, dh, dh_b16, N, HW, C, Cp, (hipStream_t)stream)); });
+}
+int df_test_pack_linear_t(const float* w, uint16_t* out, int O, int I, int ldo, int off, void* stream) {
+  return guard([&] { HIPCHK(launch_pack_linear_t(w, out, O, I, ldo, off, (hipStream_t)stream)); });
+}
+int df_test_pack_conv_bwd(const float* w, uint16_t* out, int O, int I, int Opad, void* stream) {
+  return guard([&] { HIPCHK(launch_pack_conv_bwd(w, out, O, I, Opad, (hipStream_t)stream)); });
+}
+// Backward-data of a 3x3 conv (pad 1) exactly as build_classifier_grad issues it: W_oihw fp32 [O][I][3][3] packed here with
+// Opad = O rounded up to 64 (dY: [NB][OH][OW][Opad], pad columns zero); stride 1 = conv of dY with the flipped taps, stride 2 = the
+// same over the zero-stuffed x2 grid of dY (Downsample^T).  dX fp32 [NB][H][W][I] (+ the operand-type copy dX_op when given).
+int df_test_conv3x3_bwd_data(const uint16_t* dY, const float* W_oihw, uint16_t* w_scratch, float* dX, uint16_t* dX_op, int NB, int H,
+                             int Wd, int I, int O, int stride, int tile, int splitk, void* stream) {
+  return guard([&] {
+    if (stride != 1 && stride != 2) fail("conv3x3 backward-data: stride %d", stride);
+    if (stride == 2 && ((H | Wd) & 1)) fail("conv3x3 backward-data: stride 2 needs an even map, got %dx%d", H, Wd);
+    const int Opad = (O + 63) / 64 * 64;
+    HIPCHK(launch_pack_conv_bwd(W_oihw, w_scratch, O, I, Opad, (hipStream_t)stream));
+    GemmParams g = stride == 1 ? Builder::gp_conv3(dY, NB, H, Wd, Opad, w_scratch, I, 1, 0)
+                               : Builder::gp_conv3(dY, NB, H / 2, Wd / 2, Opad, w_scratch, I, 1, 1);
+    if (stride == 2) g.zstuff = 1;
+    Builder::out_f32(g, dX, I);
+    if (dX_op) {
+      g.aux = dX_op;
+      g.ld_aux = I;
+    }
+    g.splitk = splitk;
+    if (splitk > 1) g.partial = test_partial((size_t)splitk * g.M * g.N * 4);
+    if (!gemm_tile_valid(g, tile, 1, splitk)) fail("tile %d / split-K %d refused this problem", tile, splitk);
+    HIPCHK(launch_gemm(g, tile, 1, (hipStream_t)stream));
+  });
 }
 
 }  // extern "C"

@@ -136,8 +136,16 @@ size_t attention_bwd_ws_floats(int N, int heads, int D, int Tq, int Tk, int lddk
 hipError_t launch_attention_bwd(const uint16_t* Q, int ldq, const uint16_t* K, int ldk, const uint16_t* Vt, int ldvt,
                                 const float* dO, int lddo, uint16_t* dQ, int lddq, uint16_t* dK, int lddk, uint16_t* dV,
                                 int lddv, int N, int heads, int D, int Tq, int Tk, float scale, float* ws, hipStream_t s);
+// the same with the form forced (tests): -1 = the choice above, 0 = MFMA (D 32, Tk <= 256, lddk / lddv % 4 == 0), 1 = VALU
+// LDS-resident, 2 = tiled pair (ws of N * heads * Tq * 3 floats when dK != nullptr); a form that does not take the shape fails
+hipError_t launch_attention_bwd(const uint16_t* Q, int ldq, const uint16_t* K, int ldk, const uint16_t* Vt, int ldvt,
+                                const float* dO, int lddo, uint16_t* dQ, int lddq, uint16_t* dK, int lddk, uint16_t* dV,
+                                int lddv, int N, int heads, int D, int Tq, int Tk, float scale, float* ws, int form, hipStream_t s);
+// dh = (1 - prob[n]) w / HW; prob == nullptr: the logit's cotangent is 1 (the plan applies 1 - p with launch_grad_scale_per_sample)
 hipError_t launch_cls_head_bwd(const float* prob, const float* w, float* dh, uint16_t* dh_b16, int N, int HW, int C, int Cp,
                                hipStream_t s);
+// x[n][0 .. per) *= 1 - prob[n]  (fp32, in place)
+hipError_t launch_grad_scale_per_sample(float* x, const float* prob, int N, long per, hipStream_t s);
 // Linear weight [O][I] fp32 -> transposed bf16 written at out[i*ldo + off + o]  (ldo >= off + O)
 hipError_t launch_pack_linear_t(const float* w, uint16_t* out, int O, int I, int ldo, int off, hipStream_t s);
 hipError_t launch_pack_conv_bwd(const float* w, uint16_t* out, int O, int I, int Opad, hipStream_t s);

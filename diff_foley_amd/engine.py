@@ -133,6 +133,17 @@ _SIGS = {
     "df_test_layernorm": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "df_test_attention": [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
                           C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p],
+    "df_test_groupnorm_bwd": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_int,
+                              C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+    "df_test_layernorm_bwd": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                              C.c_void_p],
+    "df_test_geglu_fwd": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p],
+    "df_test_geglu_bwd": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p],
+    "df_test_attention_bwd": [C.c_void_p, C.c_int] * 7 + [C.c_int] * 5 + [C.c_float, C.c_int, C.c_void_p],
+    "df_test_cls_head_bwd": [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p],
+    "df_test_pack_linear_t": [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p],
+    "df_test_pack_conv_bwd": [C.c_void_p, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p],
+    "df_test_conv3x3_bwd_data": [C.c_void_p] * 5 + [C.c_int] * 8 + [C.c_void_p],
     "df_test_peak": [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p],
     "df_test_fill": [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_void_p],
 }

@@ -307,6 +307,29 @@ int df_test_layernorm(const float* x_dev, int rows, int C, const float* gamma, c
                       void* stream);
 int df_test_attention(const uint16_t* Q, int ldq, const uint16_t* K, int ldk, const uint16_t* Vt, int ldvt, uint16_t* O,
                       int ldo, int N, int heads, int D, int Tq, int Tk, float scale, void* stream);
+/* The classifier's input-gradient kernels one at a time (csrc/backward.hip).  Nullable: addend, dx_b16 (its rows are C wide). */
+int df_test_groupnorm_bwd(const float* x_dev, int ld, int N, int HW, int C, const float* gamma, const float* beta, float eps,
+                          int silu, const float* dy_dev, int lddy, const float* addend_dev, int ldadd, float* dx_dev, int lddx,
+                          uint16_t* dx_b16_dev, void* stream);
+int df_test_layernorm_bwd(const float* x_dev, int rows, int C, const float* gamma, float eps, const float* dy_dev,
+                          const float* addend_dev, float* dx_dev, uint16_t* dx_b16_dev, void* stream);
+/* u = [x | gate] operand-type [rows][2H]; fwd: y = x * gelu(gate) [rows][H]; bwd: du = [dy gelu(g) | dy x gelu'(g)] [rows][2H] */
+int df_test_geglu_fwd(const uint16_t* u_dev, uint16_t* y_dev, int64_t rows, int H, void* stream);
+int df_test_geglu_bwd(const uint16_t* u_dev, const float* dy_dev, uint16_t* du_dev, int64_t rows, int H, void* stream);
+/* form: -1 the production choice, 0 MFMA, 1 VALU LDS-resident, 2 tiled pair; a forced form that does not take the shape fails.
+ * dK == NULL: dQ only (cross attention). */
+int df_test_attention_bwd(const uint16_t* Q, int ldq, const uint16_t* K, int ldk, const uint16_t* Vt, int ldvt, const float* dO,
+                          int lddo, uint16_t* dQ, int lddq, uint16_t* dK, int lddk, uint16_t* dV, int lddv, int N, int heads, int D,
+                          int Tq, int Tk, float scale, int form, void* stream);
+int df_test_cls_head_bwd(const float* prob_dev, const float* w_dev, float* dh_dev, uint16_t* dh_b16_dev, int N, int HW, int C, int Cp,
+                         void* stream);
+int df_test_pack_linear_t(const float* w_dev, uint16_t* out_dev, int O, int I, int ldo, int off, void* stream);
+int df_test_pack_conv_bwd(const float* w_dev, uint16_t* out_dev, int O, int I, int Opad, void* stream);
+/* Backward-data of a pad-1 3x3 conv as the classifier gradient runs it: dY [NB][OH][OW][rup(O, 64)] (pad columns zero), stride 1
+ * or 2 (zero-stuffed); W fp32 OIHW is packed into w_scratch (I * 9 * rup(O, 64) elements); dX fp32 [NB][H][W][I], dX_op nullable. */
+int df_test_conv3x3_bwd_data(const uint16_t* dY_dev, const float* W_oihw_dev, uint16_t* w_scratch_dev, float* dX_dev,
+                             uint16_t* dX_op_dev, int NB, int H, int Wd, int I, int O, int stride, int tile, int splitk,
+                             void* stream);
 /* Device-peak microbenchmarks (tools/peaks.py; SURVEY.md 8d "peaks measured on the box").  kind 0: MFMA issue peak
  * (n = iterations per wavefront of 4 independent v_mfma_f32_32x32x16_bf16; grid blocks x 256 threads); kind 1:
  * streaming copy of n bytes; kind 2: streaming read of n bytes. */
