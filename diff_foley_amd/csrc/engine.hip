@@ -3700,6 +3700,138 @@ int df_test_gemm_dual(const uint16_t* A, const uint16_t* A2, const uint16_t* W, 
   });
 }
 
+// Every GemmParams epilogue feature on a caller-chosen (tile, split-K, batch, gm): tests/test_gemm_epilogues_gpu.py walks the
+// autotuner's whole search space with it.
+static void test_gemm_params(const df_test_gemm_desc* d, GemmParams& g) {
+  if (!d) fail("df_test_gemm: null descriptor");
+  if (d->size != (int64_t)sizeof(df_test_gemm_desc))
+    fail("df_test_gemm: descriptor of %lld bytes, this build expects %zu (stale binding of df_test_gemm_desc?)", (long long)d->size,
+         sizeof(df_test_gemm_desc));
+  const bf16_t* A = (const bf16_t*)d->A;
+  const bf16_t* W = (const bf16_t*)d->W;
+  if (d->conv) {
+    if (d->stride != 1 && d->stride != 2) fail("df_test_gemm: conv stride %d", d->stride);
+    g = Builder::gp_conv3(A, d->NB, d->H, d->Wd, d->Cin, W, d->N, d->stride, 0);
+  } else {
+    g = Builder::gp_linear(A, d->M, d->K, W, d->N);
+    if (d->lda > 0) {
+      g.lda = d->lda;
+      g.a_bytes = Builder::op_bytes((size_t)d->M * d->lda * 2);
+    }
+  }
+  g.C = d->C; g.ldc = d->ldc > 0 ? d->ldc : g.N; g.out_bf16 = d->out_operand ? 1 : 0;
+  g.a_bs = d->a_bs; g.w_bs = d->w_bs; g.c_bs = d->c_bs; g.res_bs = d->res_bs;
+  g.alpha = d->alpha;
+  g.bias = d->bias;
+  g.rowbias = d->rowbias; g.ld_rowbias = d->ld_rowbias; g.rows_per_sample = d->rows_per_sample; g.rowbias_mode = d->rowbias_mode;
+  g.res = d->res; g.ldr = d->ldr;
+  g.relu = d->relu; g.silu = d->silu;
+  g.aux = (bf16_t*)d->aux; g.ld_aux = d->ld_aux;
+  g.stats = (float2*)d->stats; g.stats_slots = d->stats_slots;
+  g.ln_stats = (const float2*)d->ln_stats; g.ln_slots = d->ln_slots; g.ln_C = d->ln_C; g.ln_eps = d->ln_eps; g.ln_cs = d->ln_cs;
+  g.w_rows = d->w_rows; g.sm_w = d->sm_w; g.sm_valid = d->sm_valid;
+  g.dup_rows = d->dup_rows; g.no_c_store = d->no_c_store; g.store_nchw = d->store_nchw; g.hw_out = d->hw_out;
+  g.cfg_out = d->cfg_out; g.cfg_scale = d->cfg_scale;
+  g.defer_reduce = d->defer_reduce;
+  g.gm = d->gm;
+  g.splitk = d->splitk > 1 ? d->splitk : 1;
+}
+
+int df_test_gemm_valid(const df_test_gemm_desc* d, int tile, int batch, int splitk) {
+  std::lock_guard<std::recursive_mutex> hold(g_api_lock);
+  try {
+    GemmParams g;
+    test_gemm_params(d, g);
+    return gemm_tile_valid(g, tile, batch, splitk) ? 1 : 0;
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return -1;
+  }
+}
+
+int df_test_gemm_ex(const df_test_gemm_desc* d, void* stream) {
+  return guard([&] {
+    GemmParams g;
+    test_gemm_params(d, g);
+    const int batch = d->batch > 1 ? d->batch : 1;
+    if (g.K % 64 != 0) fail("df_test_gemm: K %d is not a multiple of 64", g.K);
+    if (d->defer_reduce && g.splitk < 2) fail("df_test_gemm: defer_reduce needs split-K");
+    const size_t slab_bytes = (size_t)g.splitk * g.M * g.N * 4;
+    if (g.splitk > 1) g.partial = test_partial(slab_bytes);
+    const hipError_t e = launch_gemm(g, d->tile, batch, (hipStream_t)stream);
+    if (e == hipErrorInvalidValue)
+      fail("launch_gemm refused tile %d / split-K %d / batch %d (%dx%dx%d)", d->tile, g.splitk, batch, g.M, g.N, g.K);
+    HIPCHK(e);
+    if (d->defer_reduce && d->slabs_out)
+      HIPCHK(hipMemcpyAsync(d->slabs_out, g.partial, slab_bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  });
+}
+
+// The folded cross-attention exactly as context_px + the SpatialTransformer plan run it, every intermediate returned:
+// ctx.kv (kv = ctx Wkv^T), xattn_expand (Kexp / Vexp), the lnq_t packing of (norm2.gamma, to_q) (WqT), ctx.g (G = Kexp WqT^T),
+// xattn_rowstats (cs, bb from bq = Wq beta), the batched ctx.vo (Vo[n] = Wo Vexp[n]^T), then st.xs (probabilities P from the
+// operand copy xb of the residual stream x and its per-64-column (sum, sum of squares) statistics) and st.xo (out = x + P Vo^T + bo,
+// fp32).  ctx.kv / ctx.g / ctx.vo run on the 64 x 64 tile; st.xs and st.xo on the caller's tiles.
+int df_test_xattn_chain(const uint16_t* ctx, const uint16_t* Wkv, const float* Wq, const float* gamma, const float* bq,
+                        const uint16_t* Wo, const float* bo, const float* x, const uint16_t* xb, const void* xstats, int NB, int T,
+                        int Tc, int Dc, int C, int heads, uint16_t* kv, uint16_t* Kexp, uint16_t* Vexp, uint16_t* WqT, uint16_t* G,
+                        float* cs, float* bb, uint16_t* Vo, uint16_t* P, float* out, int tile_xs, int tile_xo, void* stream) {
+  return guard([&] {
+    hipStream_t s = (hipStream_t)stream;
+    const int HT = heads * 32, M = NB * T;
+    const float scale = 1.0f / sqrtf((float)(C / heads));
+    if (Tc < 1 || Tc > 32 || C % 64 != 0 || C % heads != 0 || (C / heads) % 8 != 0 || HT % 64 != 0 || T % 64 != 0 || Dc % 64 != 0)
+      fail("xattn chain: C %d / heads %d / Tc %d / T %d / Dc %d outside what the folded form takes", C, heads, Tc, T, Dc);
+    auto run = [&](const GemmParams& g, int tile, int batch, const char* what) {
+      if (!gemm_tile_valid(g, tile, batch, 1)) fail("xattn chain: tile %d refused %s", tile, what);
+      HIPCHK(launch_gemm(g, tile, batch, s));
+    };
+    {
+      GemmParams g = Builder::gp_linear(ctx, NB * Tc, Dc, Wkv, 2 * C);
+      Builder::out_b16(g, kv, 2 * C);
+      run(g, TILE_64x64, 1, "ctx.kv");
+    }
+    HIPCHK(launch_xattn_expand(kv, Kexp, Vexp, NB, Tc, 32, C, heads, s));
+    HIPCHK(launch_pack_lnq_t(Wq, gamma, WqT, C, scale, s));
+    {
+      GemmParams g = Builder::gp_linear(Kexp, NB * HT, C, WqT, C);
+      Builder::out_b16(g, G, C);
+      run(g, TILE_64x64, 1, "ctx.g");
+    }
+    HIPCHK(launch_xattn_rowstats(G, Kexp, bq, scale, C, (long)NB * HT, cs, bb, s));
+    {
+      GemmParams g = Builder::gp_linear(Wo, C, C, Vexp, HT);
+      g.w_bs = (long)HT * C;
+      Builder::out_b16(g, Vo, HT);
+      g.c_bs = (long)C * HT;
+      run(g, TILE_64x64, NB, "ctx.vo");
+    }
+    {
+      GemmParams g = Builder::gp_linear(xb, M, C, G, HT);
+      g.w_bs = (long)HT * C; g.w_rows = T;
+      Builder::out_b16(g, P, HT);
+      g.ln_stats = (const float2*)xstats; g.ln_slots = C / 64; g.ln_C = C; g.ln_eps = 1e-5f; g.ln_cs = cs;
+      g.bias = bb;
+      g.sm_w = 32; g.sm_valid = Tc;
+      run(g, tile_xs, 1, "st.xs");
+    }
+    {
+      GemmParams g = Builder::gp_linear(P, M, HT, Vo, C);
+      g.w_bs = (long)C * HT; g.w_rows = T;
+      Builder::out_f32(g, out, C);
+      g.bias = bo;
+      g.res = x; g.ldr = C;
+      run(g, tile_xo, 1, "st.xo");
+    }
+  });
+}
+
+// FeedForward's second Linear merged with proj_out (launch_pack_ffproj): wout [C][F + C] = [Wp W2 | Wp], bout = Wp b2 + bp.
+int df_test_pack_ffproj(const float* Wp, const float* bp, const float* W2, const float* b2, uint16_t* wout, float* bout, int C, int F,
+                        void* stream) {
+  return guard([&] { HIPCHK(launch_pack_ffproj(Wp, bp, W2, b2, wout, bout, C, F, (hipStream_t)stream)); });
+}
+
 // Producer GEMM (t0 = A0 W0^T + b0 [+ t0_in], fp32 + operand copy + per-row partial statistics) followed by a
 // LayerNorm-folded consumer GEMM (y = LN(t0; gamma, beta) W1^T + b1), exactly the pair the SpatialTransformer plan uses.
 // mode 0: y fp32 [M][N1];  mode 1: GEGLU (W1 = [x ; gate] rows, y operand-type [M][N1/2]);  mode 2: fused QKV --

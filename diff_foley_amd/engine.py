@@ -28,6 +28,24 @@ def default_precision():
     return p
 
 
+class GemmDesc(C.Structure):
+    """include/df_engine.h df_test_gemm_desc (df_test_gemm_ex / df_test_gemm_valid); `size` is filled in here."""
+    _fields_ = [("size", C.c_int64), ("A", C.c_void_p), ("W", C.c_void_p), ("C", C.c_void_p)] + [
+        (n, C.c_int) for n in ("M", "N", "K", "lda", "ldc", "out_operand", "conv", "NB", "H", "Wd", "Cin", "stride", "batch", "tile",
+                               "splitk", "gm")] + [
+        (n, C.c_int64) for n in ("a_bs", "w_bs", "c_bs", "res_bs")] + [
+        ("alpha", C.c_float), ("bias", C.c_void_p), ("rowbias", C.c_void_p), ("ld_rowbias", C.c_int), ("rows_per_sample", C.c_int),
+        ("rowbias_mode", C.c_int), ("res", C.c_void_p), ("ldr", C.c_int), ("relu", C.c_int), ("silu", C.c_int), ("aux", C.c_void_p),
+        ("ld_aux", C.c_int), ("stats", C.c_void_p), ("stats_slots", C.c_int), ("ln_stats", C.c_void_p), ("ln_slots", C.c_int),
+        ("ln_C", C.c_int), ("ln_eps", C.c_float), ("ln_cs", C.c_void_p), ("w_rows", C.c_int), ("sm_w", C.c_int),
+        ("sm_valid", C.c_int), ("dup_rows", C.c_int), ("no_c_store", C.c_int), ("store_nchw", C.c_int), ("hw_out", C.c_int),
+        ("cfg_out", C.c_void_p), ("cfg_scale", C.c_float), ("defer_reduce", C.c_int), ("slabs_out", C.c_void_p)]
+
+    def __init__(self, **kw):
+        kw.setdefault("alpha", 1.0)
+        super().__init__(size=C.sizeof(GemmDesc), **kw)
+
+
 class UNetConfig(C.Structure):
     _fields_ = [("in_channels", C.c_int), ("out_channels", C.c_int), ("model_channels", C.c_int),
                 ("num_res_blocks", C.c_int), ("channel_mult", C.c_int * 8), ("n_mult", C.c_int),
@@ -144,6 +162,10 @@ _SIGS = {
     "df_test_pack_linear_t": [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p],
     "df_test_pack_conv_bwd": [C.c_void_p, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p],
     "df_test_conv3x3_bwd_data": [C.c_void_p] * 5 + [C.c_int] * 8 + [C.c_void_p],
+    "df_test_gemm_ex": [C.POINTER(GemmDesc), C.c_void_p],
+    "df_test_gemm_valid": [C.POINTER(GemmDesc), C.c_int, C.c_int, C.c_int],
+    "df_test_xattn_chain": [C.c_void_p] * 10 + [C.c_int] * 6 + [C.c_void_p] * 10 + [C.c_int, C.c_int, C.c_void_p],
+    "df_test_pack_ffproj": [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p],
     "df_test_peak": [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p],
     "df_test_fill": [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_void_p],
 }

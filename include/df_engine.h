@@ -330,6 +330,46 @@ int df_test_pack_conv_bwd(const float* w_dev, uint16_t* out_dev, int O, int I, i
 int df_test_conv3x3_bwd_data(const uint16_t* dY_dev, const float* W_oihw_dev, uint16_t* w_scratch_dev, float* dX_dev,
                              uint16_t* dX_op_dev, int NB, int H, int Wd, int I, int O, int stride, int tile, int splitk,
                              void* stream);
+/* One GEMM with any GemmParams epilogue (csrc/gemm.h) switched on, on a caller-chosen (tile, split-K, batch, gm): the tests of the
+ * autotuner's search space.  `size` must be sizeof(df_test_gemm_desc).  Geometry: conv == 0 linear, A [M][lda] (lda 0 = K);
+ * conv == 1 a pad-1 3x3 conv, A NHWC [NB][H][Wd][Cin], W [N][9][Cin], M = NB * OH * OW.  Null / zero fields are off.  ldc 0 = N.
+ * defer_reduce (split-K only): the slabs are left for a consumer; when slabs_out is given they are copied there,
+ * [splitk][M][N] fp32.  Refusals of launch_gemm are reported as "launch_gemm refused ..." through df_last_error. */
+typedef struct df_test_gemm_desc {
+  int64_t size;
+  const void* A; const void* W; void* C;
+  int M, N, K, lda, ldc, out_operand;
+  int conv, NB, H, Wd, Cin, stride;
+  int batch, tile, splitk, gm;
+  int64_t a_bs, w_bs, c_bs, res_bs;
+  float alpha;
+  const float* bias;
+  const float* rowbias; int ld_rowbias, rows_per_sample, rowbias_mode;
+  const float* res; int ldr;
+  int relu, silu;
+  void* aux; int ld_aux;
+  void* stats; int stats_slots;                 /* float2 [rows][stats_slots] */
+  const void* ln_stats; int ln_slots, ln_C; float ln_eps; const float* ln_cs;
+  int w_rows, sm_w, sm_valid;
+  int dup_rows, no_c_store, store_nchw, hw_out;
+  float* cfg_out; float cfg_scale;
+  int defer_reduce; float* slabs_out;
+} df_test_gemm_desc;
+int df_test_gemm_ex(const df_test_gemm_desc* d, void* stream);
+/* gemm_tile_valid(d, tile, batch, splitk): 1 / 0, or -1 (message in df_last_error) for a malformed descriptor.  Host only. */
+int df_test_gemm_valid(const df_test_gemm_desc* d, int tile, int batch, int splitk);
+/* The folded cross-attention of one SpatialTransformer (engine.hip context_px, st.xs, st.xo), every intermediate out: ctx [NB*Tc][Dc]
+ * and Wkv [2C][Dc] (to_k | to_v) operand type; Wq [C][C], gamma (norm2), bq = Wq . beta fp32; Wo [C][C] operand, bo fp32; x fp32
+ * [NB*T][C], xb its operand copy, xstats float2 [NB*T][C/64] (sum, sum of squares per 64 columns).  Outputs: kv [NB*Tc][2C],
+ * Kexp / Vexp [NB][H*32][C], WqT [C][C], G [NB][H*32][C], cs / bb [NB][H*32], Vo [NB][C][H*32], P [NB*T][H*32], out fp32 [NB*T][C]. */
+int df_test_xattn_chain(const uint16_t* ctx_dev, const uint16_t* Wkv_dev, const float* Wq_dev, const float* gamma_dev,
+                        const float* bq_dev, const uint16_t* Wo_dev, const float* bo_dev, const float* x_dev, const uint16_t* xb_dev,
+                        const void* xstats_dev, int NB, int T, int Tc, int Dc, int C, int heads, uint16_t* kv_dev, uint16_t* Kexp_dev,
+                        uint16_t* Vexp_dev, uint16_t* WqT_dev, uint16_t* G_dev, float* cs_dev, float* bb_dev, uint16_t* Vo_dev,
+                        uint16_t* P_dev, float* out_dev, int tile_xs, int tile_xo, void* stream);
+/* [Wp.W2 | Wp] operand [C][F + C] and bias Wp.b2 + bp (FeedForward's second Linear merged with proj_out). */
+int df_test_pack_ffproj(const float* Wp_dev, const float* bp_dev, const float* W2_dev, const float* b2_dev, uint16_t* wout_dev,
+                        float* bout_dev, int C, int F, void* stream);
 /* Device-peak microbenchmarks (tools/peaks.py; SURVEY.md 8d "peaks measured on the box").  kind 0: MFMA issue peak
  * (n = iterations per wavefront of 4 independent v_mfma_f32_32x32x16_bf16; grid blocks x 256 threads); kind 1:
  * streaming copy of n bytes; kind 2: streaming read of n bytes. */

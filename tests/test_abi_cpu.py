@@ -48,6 +48,29 @@ def test_built_libraries_pass_the_layout_checks():
     assert r.returncode == 0 and "0 hazard(s)" in r.stdout, r.stdout + r.stderr
 
 
+def test_gemm_desc_binding_matches_the_build():
+    """The ctypes mirror of df_test_gemm_desc has the C struct's size (the entries check `size` and refuse any other value before
+    touching the GPU), and the validity query answers on the host: a K = 4096 linear takes split-K 32 on the generic tiles and
+    never on a halo tile; the cross-attention score epilogue refuses split-K."""
+    import ctypes as C
+    for prec in ("bf16", "fp16"):
+        L = E.lib(prec)
+        d = E.GemmDesc(M=256, N=128, K=4096)
+        assert L.df_test_gemm_valid(C.byref(d), 0, 1, 32) == 1
+        assert L.df_test_gemm_valid(C.byref(d), 5, 1, 1) == 0
+        one = (C.c_float * 4096)()
+        xs = E.GemmDesc(M=256, N=128, K=192, out_operand=1, ln_stats=C.addressof(one), ln_slots=3, ln_C=192, ln_cs=C.addressof(one),
+                        bias=C.addressof(one), w_rows=128, sm_w=32, sm_valid=17)
+        assert L.df_test_gemm_valid(C.byref(xs), 0, 1, 1) == 1
+        assert L.df_test_gemm_valid(C.byref(xs), 0, 1, 2) == 0
+        bad = E.GemmDesc(M=256, N=128, K=4096)
+        bad.size = C.sizeof(bad) - 8
+        assert L.df_test_gemm_valid(C.byref(bad), 0, 1, 1) == -1
+        assert b"descriptor" in L.df_last_error()
+        assert L.df_test_gemm_ex(C.byref(bad), None) != 0
+        assert b"descriptor" in L.df_last_error()
+
+
 def test_no_gpu_fails_loudly():
     if torch.cuda.is_available():
         pytest.skip("GPU present")
