@@ -745,10 +745,8 @@ struct Builder {
     pl->release(a1);
     // h1 has ONE consumer, the second GroupNorm.  When conv1 runs split-K, its reduce launch is dropped: the norm sums
     // the partial slabs while loading and adds the bias / FiLM bias itself (no reduce kernel, no fp32 round trip of h1).
-    constexpr bool no_defer = false;
     const size_t ci = pl->ops.size() - 1;
-    const bool can_defer = !no_defer && groupnorm_accepts_slabs(H * Wd, cout);
-    pl->ops[ci].defer = can_defer;
+    pl->ops[ci].defer = groupnorm_accepts_slabs(H * Wd, cout);
     bf16_t* a2 = buf<bf16_t>((size_t)M * cout);
     {
       Plan* plp = pl;
@@ -771,20 +769,11 @@ struct Builder {
       pl->release(scr);
     }
     pl->release(h1);
-    constexpr bool no_skipfold = false;
-    const bool fold_skip = has_skip && !no_skipfold && cin % 64 == 0;
-    if (has_skip && !fold_skip) {
-      GemmParams g = gp_linear(xraw, M, cin, c->w_linear(nm(skip + ".weight")), cout);
-      out_f32(g, out.p, out.ld);
-      g.bias = c->f32(nm(skip + ".bias"));
-      gemm(g, 1, "res.skip");
-      pl->release(xraw);
-    }
     {
       GemmParams g = gp_conv3(a2, NB, H, Wd, cout, c->w_conv3(nm(c2 + ".weight"), cout), cout, 1, 0);
       out_f32(g, out.p, out.ld);
       g.bias = c->f32(nm(c2 + ".bias"));
-      if (fold_skip) {
+      if (has_skip) {
         // skip(x) + conv2(h) as ONE implicit GEMM: the 1x1 skip conv is a tenth K range over the raw operand copy of x
         const bf16_t* w;
         const float* bsum;
@@ -794,113 +783,13 @@ struct Builder {
         g.A2 = xraw; g.lda2 = cin; g.Cin2 = cin; g.a2_bytes = op_bytes((size_t)M * cin * 2);
         g.K = 9 * cout + cin;
         g.w_bytes = op_bytes((size_t)cout * g.K * 2);
-      } else if (has_skip) { g.res = out.p; g.ldr = out.ld; } else { g.res = x.p; g.ldr = x.ld; }
+      } else { g.res = x.p; g.ldr = x.ld; }
       attach_aux(g, M, cout);
       g.dup_rows = dup_rows;       // CFG prefix: this block ran on one half of the batch, its output feeds both
       gemm(g, 1, "res.conv2");
     }
-    if (fold_skip) pl->release(xraw);
+    if (has_skip) pl->release(xraw);
     pl->release(a2);
-  }
-
-  // The same block as separate launches -- LayerNorm kernels, K|Q and V^T projections apart (env DF_NO_LNFOLD=1):
-  // kept as the A/B reference for the folded plan below.
-  void spatial_transformer_unfused(const F32& x, const F32& out, int NB, int T, const std::string& p, int heads,
-                           const bf16_t* ctxK, const bf16_t* ctxVt, int Tc, int ldvtc) {
-    const int C = x.C, M = x.rows, D = C / heads;
-    if (!attention_supported(D)) fail("unsupported attention head dim %d", D);
-    const std::string tb = p + ".transformer_blocks.0";
-    const float scale = 1.0f / sqrtf((float)D);
-    bf16_t* a = groupnorm(x, NB, p + ".norm", 1e-6f, 0, nullptr);
-    float* t0 = buf<float>((size_t)M * C);
-    F32 t0v{t0, M, C, C};
-    {
-      GemmParams g = gp_linear(a, M, C, c->w_linear(nm(p + ".proj_in.weight")), C);
-      out_f32(g, t0, C);
-      g.bias = c->f32(nm(p + ".proj_in.bias"));
-      gemm(g, 1, "st.proj_in");
-    }
-    // ---- self attention
-    layernorm(t0v, tb + ".norm1", a);
-    bf16_t* qk = buf<bf16_t>((size_t)M * 2 * C);
-    {
-      const bf16_t* w = c->w_stack(nm(tb + ".attn1.qk"), {nm(tb + ".attn1.to_q.weight"), nm(tb + ".attn1.to_k.weight")});
-      GemmParams g = gp_linear(a, M, C, w, 2 * C);
-      out_b16(g, qk, 2 * C);
-      gemm(g, 1, "st.qk");
-    }
-    const int ldvt = rup(T, 32);
-    bf16_t* vt = buf<bf16_t>((size_t)NB * C * ldvt);
-    {  // V^T[n] = Wv . a[n]^T  (batched: A = Wv shared, "W" operand = this sample's tokens)
-      GemmParams g = gp_linear(c->w_linear(nm(tb + ".attn1.to_v.weight")), C, C, a, T);
-      g.w_bs = (long)T * C;
-      out_b16(g, vt, ldvt);
-      g.c_bs = (long)C * ldvt;
-      gemm(g, NB, "st.vT");
-    }
-    bf16_t* o = buf<bf16_t>((size_t)M * C);
-    other("attn.self", [=](hipStream_t s, const RunArgs&) {
-      return launch_attention(qk, 2 * C, qk + C, 2 * C, vt, ldvt, o, C, NB, heads, D, T, T, scale, s);
-    });
-    {
-      GemmParams g = gp_linear(o, M, C, c->w_linear(nm(tb + ".attn1.to_out.0.weight")), C);
-      out_f32(g, t0, C);
-      g.bias = c->f32(nm(tb + ".attn1.to_out.0.bias"));
-      g.res = t0; g.ldr = C;
-      gemm(g, 1, "st.attn1.out");
-    }
-    // ---- cross attention (K / V^T of the context were computed by set_context)
-    layernorm(t0v, tb + ".norm2", a);
-    bf16_t* q2 = qk;
-    {
-      GemmParams g = gp_linear(a, M, C, c->w_linear(nm(tb + ".attn2.to_q.weight")), C);
-      out_b16(g, q2, C);
-      gemm(g, 1, "st.q2");
-    }
-    other("attn.cross", [=](hipStream_t s, const RunArgs&) {
-      return launch_attention(q2, C, ctxK, C, ctxVt, ldvtc, o, C, NB, heads, D, T, Tc, scale, s);
-    });
-    {
-      GemmParams g = gp_linear(o, M, C, c->w_linear(nm(tb + ".attn2.to_out.0.weight")), C);
-      out_f32(g, t0, C);
-      g.bias = c->f32(nm(tb + ".attn2.to_out.0.bias"));
-      g.res = t0; g.ldr = C;
-      gemm(g, 1, "st.attn2.out");
-    }
-    pl->release(qk);
-    pl->release(vt);
-    pl->release(o);
-    // ---- GEGLU feed-forward
-    layernorm(t0v, tb + ".norm3", a);
-    bf16_t* gl = buf<bf16_t>((size_t)M * 4 * C);
-    {
-      const bf16_t* w;
-      const float* b;
-      c->w_geglu(nm(tb + ".ff.net.0.proj"), &w, &b);
-      GemmParams g = gp_linear(a, M, C, w, 8 * C);
-      out_b16(g, gl, 4 * C);
-      g.bias = b;
-      g.geglu = 1;
-      gemm(g, 1, "st.ff1");
-    }
-    {
-      GemmParams g = gp_linear(gl, M, 4 * C, c->w_linear(nm(tb + ".ff.net.2.weight")), C);
-      out_b16(g, a, C);            // transformer output, consumed only by proj_out
-      g.bias = c->f32(nm(tb + ".ff.net.2.bias"));
-      g.res = t0; g.ldr = C;
-      gemm(g, 1, "st.ff2");
-    }
-    pl->release(gl);
-    {
-      GemmParams g = gp_linear(a, M, C, c->w_linear(nm(p + ".proj_out.weight")), C);
-      out_f32(g, out.p, out.ld);
-      g.bias = c->f32(nm(p + ".proj_out.bias"));
-      g.res = x.p; g.ldr = x.ld;
-      attach_aux(g, M, C);
-      gemm(g, 1, "st.proj_out");
-    }
-    pl->release(a);
-    pl->release(t0);
   }
 
   // SpatialTransformer (attention_openai.py:250-261) with one BasicTransformerBlock (:211-215).
@@ -911,8 +800,6 @@ struct Builder {
   void spatial_transformer(const F32& x, const F32& out, int NB, int T, const std::string& p, int heads,
                            const bf16_t* ctxK, const bf16_t* ctxVt, int Tc, int ldvtc, const PX* px = nullptr,
                            bool cfg_prefix = false) {
-    constexpr bool no_fold = false;
-    if (no_fold) return spatial_transformer_unfused(x, out, NB, T, p, heads, ctxK, ctxVt, Tc, ldvtc);
     const int C = x.C, M = x.rows, D = C / heads;
     if (cfg_prefix && (T % 4 != 0 || NB % 2 != 0)) fail("cfg prefix needs the fused QKV form");
     const int Mp = cfg_prefix ? M / 2 : M, NBp = cfg_prefix ? NB / 2 : NB;     // rows / samples of the deduplicated prefix
@@ -1013,8 +900,7 @@ struct Builder {
         produces_t0(g);
         // nobody reads the fp32 residual stream after this op on the merged-FF path (FF1 and ffproj consume the operand
         // copy + row statistics, the block residual is x): the epilogue skips the fp32 store
-        if (C % 64 == 0)
-          g.no_c_store = 1;
+        g.no_c_store = 1;
         g.bias = c->f32(nm(tb + ".attn2.to_out.0.bias"));
         g.res = t0; g.ldr = C;
         gemm(g, 1, "st.xo");
@@ -1064,8 +950,7 @@ struct Builder {
       }
       gemm(g, 1, "st.ff1");
     }
-    constexpr bool no_ffproj = false;
-    if (!no_ffproj && C % 64 == 0) {
+    {
       // FF's second Linear, the residual add and proj_out are ONE linear map of (h, t): proj_out(t + W2 h + b2) =
       // (Wp W2) h + Wp t + (Wp b2 + bp).  One GEMM with K = 4C + C over two A tensors -- the GEGLU output and the operand
       // copy of the residual stream -- with the same FLOPs as the pair it replaces and one launch fewer per block.
@@ -1081,30 +966,8 @@ struct Builder {
       g.res = x.p; g.ldr = x.ld;
       attach_aux(g, M, C);
       gemm(g, 1, "st.ffproj");
-      pl->release(gl);
-      pl->release(a);
-      pl->release(t0);
-      pl->release(xb);
-      pl->release(st);
-      pl->release(o_own);
-      return;
-    }
-    {
-      GemmParams g = gp_linear(gl, M, 4 * C, c->w_linear(nm(tb + ".ff.net.2.weight")), C);
-      out_b16(g, a, C);            // transformer output, consumed only by proj_out
-      g.bias = c->f32(nm(tb + ".ff.net.2.bias"));
-      g.res = t0; g.ldr = C;
-      gemm(g, 1, "st.ff2");
     }
     pl->release(gl);
-    {
-      GemmParams g = gp_linear(a, M, C, c->w_linear(nm(p + ".proj_out.weight")), C);
-      out_f32(g, out.p, out.ld);
-      g.bias = c->f32(nm(p + ".proj_out.bias"));
-      g.res = x.p; g.ldr = x.ld;
-      attach_aux(g, M, C);
-      gemm(g, 1, "st.proj_out");
-    }
     pl->release(a);
     pl->release(t0);
     pl->release(xb);
@@ -1306,7 +1169,7 @@ struct NetState {                 // context-dependent buffers shared between se
   int ldvt = 0;
 };
 
-void build_unet_like(df_ctx* c, Plan* pl, int which, int N, int H, int W, int Tc, bool cfg_mode, bool ctx_inline) {
+void build_unet_like(df_ctx* c, Plan* pl, int which, int N, int H, int W, int Tc, bool cfg_mode) {
   const df_unet_config& u = which ? c->ccfg : c->ucfg;
   const std::string pre = which ? "classifier.model." : "model.diffusion_model.";
   Builder b{c, pl, pre, which};
@@ -1320,8 +1183,6 @@ void build_unet_like(df_ctx* c, Plan* pl, int which, int N, int H, int W, int Tc
   bf16_t* ctxb = b.buf<bf16_t>((size_t)N * Tc * Dc);
   std::map<std::string, std::pair<bf16_t*, bf16_t*>> kv;
   std::map<std::string, Builder::PX> pxs;
-  constexpr bool no_lnfold = false;
-  const size_t ctx_ops_begin = pl->ops.size();
   {
     const long n = (long)N * Tc * Dc;
     b.other("ctx.cast", [=](hipStream_t s, const RunArgs& a) { return launch_cast_bf16(a.aux, ctxb, n, s); });
@@ -1329,7 +1190,7 @@ void build_unet_like(df_ctx* c, Plan* pl, int which, int N, int H, int W, int Tc
       const int tokens = (H / d.ds) * (W / d.ds);
       // the denoiser's context is set once per sample() call: fold it into per-sample operands where the shapes allow;
       // the classifier gets new features with every call and keeps the K / V^T form
-      if (which == 0 && !no_lnfold && Builder::px_ok(d.cin, heads, Tc, tokens)) {
+      if (which == 0 && Builder::px_ok(d.cin, heads, Tc, tokens)) {
         pxs[d.prefix] = b.context_px(ctxb, N, Tc, Dc, d.prefix, d.cin, heads);
         kv[d.prefix] = {nullptr, nullptr};
         continue;
@@ -1339,18 +1200,10 @@ void build_unet_like(df_ctx* c, Plan* pl, int which, int N, int H, int W, int Tc
       kv[d.prefix] = {K, Vt};
     }
   }
-  const size_t ctx_ops_end = pl->ops.size();
-  pl->n_ctx = ctx_ops_end;
-  if (!ctx_inline) {
-    // move the context ops into a separate plan entry "…#ctx" is handled by the caller: it splits [begin,end)
-  }
-  (void)ctx_ops_begin;
-  (void)ctx_ops_end;
+  pl->n_ctx = pl->ops.size();
 
   // ---- time embedding MLP and the fused emb projection of every ResBlock
   const int B_ext = cfg_mode ? N / 2 : N;
-  float* e1 = b.buf<float>((size_t)N * temb);
-  float* semb = b.buf<float>((size_t)N * temb);
   const int etot = c->emb_total[which];
   float* E = b.buf<float>((size_t)N * etot);
   pl->op_t0 = (long)pl->ops.size();
@@ -1366,62 +1219,36 @@ void build_unet_like(df_ctx* c, Plan* pl, int which, int N, int H, int W, int Tc
     }
     const bf16_t* w = c->w_stack(pre + "#embw", wn);
     const float* bb = c->b_stack(pre + "#embb", bn);
-    constexpr bool emb_mfma = true;
-    if (emb_mfma && mc % 64 == 0) {
-      // The time-embedding MLP and the stacked emb projections as three MFMA GEMMs (M = N rows, rows beyond M are
-      // out-of-bounds zero fill): the 52 MB emb weight stream goes through the LDS-DMA ring of the GEMM kernel at the HBM
-      // rate, where the GEMV kernels reach 0.9 TB/s.  Activations take the operand type here (they are O(1) sinusoids /
-      // SiLU outputs; the projections' fp32 results E are what the ResBlocks consume).
-      bf16_t* teb = b.buf<bf16_t>((size_t)N * mc);
-      bf16_t* e1b = b.buf<bf16_t>((size_t)N * temb);
-      bf16_t* seb = b.buf<bf16_t>((size_t)N * temb);
-      b.other("t.embed", [=](hipStream_t s, const RunArgs& a) { return launch_timestep_embedding_b16(a.t, B_ext, teb, N, mc, s); });
-      {
-        GemmParams g = Builder::gp_linear(teb, N, mc, w0, temb);
-        Builder::out_b16(g, e1b, temb);
-        g.bias = b0; g.silu = 1;
-        b.gemm(g, 1, "t.mlp0");
-      }
-      {
-        GemmParams g = Builder::gp_linear(e1b, N, temb, w2, temb);
-        Builder::out_b16(g, seb, temb);
-        g.bias = b2; g.silu = 1;          // emb is only ever consumed through SiLU (emb_layers = SiLU -> Linear)
-        b.gemm(g, 1, "t.mlp2");
-      }
-      {
-        GemmParams g = Builder::gp_linear(seb, N, temb, w, etot);
-        Builder::out_f32(g, E, etot);
-        g.bias = bb;
-        b.gemm(g, 1, "t.embproj");
-      }
-    } else if (N <= 16) {
-      // three weight-streaming launches: [timestep embedding (CFG duplication folded in) -> Linear -> SiLU] (LDS-staged
-      // activations), [Linear -> SiLU] (emb is only ever consumed through SiLU: emb_layers = SiLU -> Linear), and the
-      // stacked emb_layers projections of all ResBlocks (register kernel: measured faster for the 52 MB stream)
-      b.other("t.mlp0", [=](hipStream_t s, const RunArgs& a) {
-        return launch_linear_rows_lds(nullptr, 0, a.t, B_ext, w0, b0, e1, temb, N, temb, mc, 1, s);
-      });
-      b.other("t.mlp2", [=](hipStream_t s, const RunArgs&) { return launch_linear_rows(e1, temb, w2, b2, semb, temb, N, temb, temb, 1, s); });
-      b.other("t.embproj", [=](hipStream_t s, const RunArgs&) { return launch_linear_rows(semb, temb, w, bb, E, etot, N, etot, temb, 0, s); });
-    } else {
-      float* tbuf = b.buf<float>(N);
-      b.other("t.copy", [=](hipStream_t s, const RunArgs& a) {
-        hipError_t e = hipMemcpyAsync(tbuf, a.t, (size_t)B_ext * 4, hipMemcpyDeviceToDevice, s);
-        if (e != hipSuccess) return e;
-        if (cfg_mode) e = hipMemcpyAsync(tbuf + B_ext, a.t, (size_t)B_ext * 4, hipMemcpyDeviceToDevice, s);
-        return e;
-      });
-      float* te = b.buf<float>((size_t)N * mc);
-      b.other("t.embed", [=](hipStream_t s, const RunArgs&) { return launch_timestep_embedding(tbuf, te, N, mc, s); });
-      b.other("t.mlp0", [=](hipStream_t s, const RunArgs&) { return launch_linear_rows(te, mc, w0, b0, e1, temb, N, temb, mc, 1, s); });
-      b.other("t.mlp2", [=](hipStream_t s, const RunArgs&) { return launch_linear_rows(e1, temb, w2, b2, semb, temb, N, temb, temb, 1, s); });
-      b.other("t.embproj", [=](hipStream_t s, const RunArgs&) { return launch_linear_rows(semb, temb, w, bb, E, etot, N, etot, temb, 0, s); });
+    // The time-embedding MLP and the stacked emb projections as three MFMA GEMMs (M = N rows, rows beyond M are
+    // out-of-bounds zero fill): the 52 MB emb weight stream goes through the LDS-DMA ring of the GEMM kernel at the HBM
+    // rate, where the GEMV kernels reach 0.9 TB/s.  Activations take the operand type here (they are O(1) sinusoids /
+    // SiLU outputs; the projections' fp32 results E are what the ResBlocks consume).
+    bf16_t* teb = b.buf<bf16_t>((size_t)N * mc);
+    bf16_t* e1b = b.buf<bf16_t>((size_t)N * temb);
+    bf16_t* seb = b.buf<bf16_t>((size_t)N * temb);
+    b.other("t.embed", [=](hipStream_t s, const RunArgs& a) { return launch_timestep_embedding_b16(a.t, B_ext, teb, N, mc, s); });
+    {
+      GemmParams g = Builder::gp_linear(teb, N, mc, w0, temb);
+      Builder::out_b16(g, e1b, temb);
+      g.bias = b0; g.silu = 1;
+      b.gemm(g, 1, "t.mlp0");
+    }
+    {
+      GemmParams g = Builder::gp_linear(e1b, N, temb, w2, temb);
+      Builder::out_b16(g, seb, temb);
+      g.bias = b2; g.silu = 1;          // emb is only ever consumed through SiLU (emb_layers = SiLU -> Linear)
+      b.gemm(g, 1, "t.mlp2");
+    }
+    {
+      GemmParams g = Builder::gp_linear(seb, N, temb, w, etot);
+      Builder::out_f32(g, E, etot);
+      g.bias = bb;
+      b.gemm(g, 1, "t.embproj");
     }
     pl->weight_bytes += 2.0 * etot * temb + 2.0 * (temb * mc + temb * temb);
   }
   // (round 5) a hoisted step's two leading launches -- the table look-up and the latent packing -- are one launch
-  constexpr bool no_step_merge = false;
-  const bool step_merge = !no_step_merge && !which && etot % 4 == 0;
+  const bool step_merge = !which && etot % 4 == 0;
   if (!which && etot % 4 == 0) {
     // the table look-up that replaces the ops above when the caller announced its timesteps (df_unet_set_timesteps): the time
     // embedding depends on t only, so a sampler computes it for all S steps before the loop, like the context operands
@@ -1444,8 +1271,7 @@ void build_unet_like(df_ctx* c, Plan* pl, int which, int N, int H, int W, int Tc
   // cross-attention -- conv_in, the first ResBlock, and the first SpatialTransformer up to its self-attention out-projection --
   // is identical in both halves.  Those ops run on ONE half; the ops whose outputs the full batch needs (conv_in -> skip +
   // ResBlock, ResBlock -> transformer residual, attn1.out -> residual stream) store every row twice (GemmParams::dup_rows).
-  constexpr bool no_dedup = false;
-  const bool dedup = cfg_mode && !which && !no_dedup && !no_lnfold && N % 2 == 0 && topo.input.size() >= 2 &&
+  const bool dedup = cfg_mode && !which && N % 2 == 0 && topo.input.size() >= 2 &&
                      topo.input[0].size() == 1 && topo.input[0][0].kind == BlockDesc::CONV_IN && topo.input[1].size() == 2 &&
                      topo.input[1][0].kind == BlockDesc::RES && topo.input[1][1].kind == BlockDesc::ST && (HW % 4) == 0 &&
                      pxs.count(topo.input[1][1].prefix) > 0;
@@ -1534,11 +1360,8 @@ void build_unet_like(df_ctx* c, Plan* pl, int which, int N, int H, int W, int Tc
         dst = mk(h.rows * 4, d.cout);
         bf16_t* hb = in_aux ? in_aux : b.cast2d(h);
         // Upsample (openai_unetmodel.py:100-119): four 2x2-tap convs on the input-resolution map instead of a 3x3 conv on
-        // the x2 map (2.25x fewer multiply-adds, gemm_m3.hip); DF_NO_UPS4=1 keeps the 3x3 form (A/B, parity tests)
-        constexpr bool no_ups4 = false;
-        GemmParams g = (!no_ups4 && d.cin % 64 == 0)
-                           ? Builder::gp_conv3_ups4(hb, N, hh, ww, d.cin, c->w_conv3_ups4(pre + d.prefix + ".conv.weight", d.cin), d.cout)
-                           : Builder::gp_conv3(hb, N, hh, ww, d.cin, c->w_conv3(pre + d.prefix + ".conv.weight", d.cin), d.cout, 1, 1);
+        // the x2 map (2.25x fewer multiply-adds, gemm_m3.hip)
+        GemmParams g = Builder::gp_conv3_ups4(hb, N, hh, ww, d.cin, c->w_conv3_ups4(pre + d.prefix + ".conv.weight", d.cin), d.cout);
         Builder::out_f32(g, dst.p, dst.ld);
         g.bias = c->f32(pre + d.prefix + ".conv.bias");
         b.gemm(g, 1, "up");
@@ -1603,9 +1426,8 @@ void build_unet_like(df_ctx* c, Plan* pl, int which, int N, int H, int W, int Tc
     float* e2 = b.buf<float>((size_t)N * u.out_channels * HW);
     Builder::out_f32(g, e2, u.out_channels);
     // (round 5) when the tuner runs out.conv split-K, its reduce launch forms the guided eps as well (gemm.hip
-    // splitk_reduce_cfg_kernel: same arithmetic, one launch fewer); cfg.combine then has nothing to do.  DF_NO_STEP_MERGE=1 reverts.
-    Op& oc_ = b.gemm(g, 1, "out.conv");
-    oc_.cfg_ext = !no_step_merge;
+    // splitk_reduce_cfg_kernel: same arithmetic, one launch fewer); cfg.combine then has nothing to do.
+    b.gemm(g, 1, "out.conv").cfg_ext = true;
     const size_t oci = pl->ops.size() - 1;
     Plan* plq = pl;
     const long n = (long)(N / 2) * u.out_channels * HW;
@@ -2131,9 +1953,7 @@ void build_vae(df_ctx* c, Plan* pl, int B, int H, int W) {
       bf16_t* hb = b.cast2d(h);
       F32 o{b.buf<float>((size_t)h.rows * 4 * co), h.rows * 4, co, co};
       const std::string p = pre + "decoder.up." + std::to_string(lvl) + ".upsample.conv";
-      constexpr bool no_ups4 = false;
-      GemmParams g = (!no_ups4 && co % 64 == 0) ? Builder::gp_conv3_ups4(hb, B, hh, ww, co, c->w_conv3_ups4(p + ".weight", co), co)
-                                                : Builder::gp_conv3(hb, B, hh, ww, co, c->w_conv3(p + ".weight", co), co, 1, 1);
+      GemmParams g = Builder::gp_conv3_ups4(hb, B, hh, ww, co, c->w_conv3_ups4(p + ".weight", co), co);
       Builder::out_f32(g, o.p, co);
       g.bias = c->f32(p + ".bias");
       b.gemm(g, 1, "vae.up");
@@ -2145,8 +1965,7 @@ void build_vae(df_ctx* c, Plan* pl, int B, int H, int W) {
     }
   }
   bf16_t* a = b.groupnorm(h, B, "decoder.norm_out", 1e-6f, 1, nullptr);
-  constexpr bool no_fewout = false;
-  if (!no_fewout && conv3x3_fewout_ok(hh, ww, h.C, v.out_ch)) {
+  if (conv3x3_fewout_ok(hh, ww, h.C, v.out_ch)) {
     const bf16_t* wp = c->w_conv3(pre + "decoder.conv_out.weight", h.C);
     const float* bo = c->f32(pre + "decoder.conv_out.bias");
     const int H_ = hh, W_ = ww, C_ = h.C, O_ = v.out_ch;
@@ -2702,30 +2521,33 @@ void autotune_plan(df_ctx* c, Plan* pl, hipStream_t s) {
   a.out = (float*)(ext + 3 * slab);
   a.out2 = (float*)(ext + 4 * slab);
   const bool prof_was = c->prof_on;
-  const int reps = 3;
-  constexpr bool tune_pair = true;
+  // per-op minimum over `nrep` in-plan runs of the whole plan (a first run warms up)
+  auto time_ops = [&](int nrep) {
+    std::vector<float> best(pl->ops.size(), 1e30f);
+    for (int rep = 0; rep < nrep + 1; ++rep) {
+      c->prof_on = true;
+      c->prof_used = 0;
+      c->prof_fam.clear();
+      c->prof_op.clear();
+      run_ops(c, pl, 0, pl->ops.size(), s, a);
+      c->prof_on = false;
+      HIPCHK(hipStreamSynchronize(s));
+      if (rep == 0) continue;
+      for (size_t i = 0; i < pl->ops.size(); ++i) {
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, c->prof_ev[2 * i], c->prof_ev[2 * i + 1]));
+        best[i] = std::min(best[i], ms);
+      }
+    }
+    return best;
+  };
   // one in-plan pass over candidate ranks [0, nr): every GEMM class runs its r-th candidate, per-op minimum over `nrep` runs
   auto evaluate = [&](size_t nr, int nrep) {
     for (auto& kv : cands)
       for (auto& cd : kv.second) cd.situ_ms = 0.0;
     for (size_t r = 0; r < nr; ++r) {
       apply((int)r);
-      std::vector<float> best(pl->ops.size(), 1e30f);
-      for (int rep = 0; rep < nrep + 1; ++rep) {   // first repetition warms up
-        c->prof_on = true;
-        c->prof_used = 0;
-        c->prof_fam.clear();
-        c->prof_op.clear();
-        run_ops(c, pl, 0, pl->ops.size(), s, a);
-        c->prof_on = false;
-        HIPCHK(hipStreamSynchronize(s));
-        if (rep == 0) continue;
-        for (size_t i = 0; i < pl->ops.size(); ++i) {
-          float ms = 0;
-          HIPCHK(hipEventElapsedTime(&ms, c->prof_ev[2 * i], c->prof_ev[2 * i + 1]));
-          best[i] = std::min(best[i], ms);
-        }
-      }
+      const std::vector<float> best = time_ops(nrep);
       for (size_t i = 0; i < pl->ops.size(); ++i) {
         const Op& o = pl->ops[i];
         if (!o.is_gemm || o.c_ext) continue;
@@ -2733,7 +2555,7 @@ void autotune_plan(df_ctx* c, Plan* pl, hipStream_t s) {
         // a deferred split-K reduce is paid by the next op (the GroupNorm sums the slabs): judge the pair.  (round 5) Any consumer
         // that is not a GEMM itself (GroupNorm, attention: their time depends on nothing in this round but where this GEMM's tile
         // walk left their input -- which XCD's L2 holds it) is judged with its producer too.
-        const bool pair = i + 1 < pl->ops.size() && (o.defer || (tune_pair && !pl->ops[i + 1].is_gemm));
+        const bool pair = i + 1 < pl->ops.size() && (o.defer || !pl->ops[i + 1].is_gemm);
         if (r < v.size()) v[r].situ_ms += best[i] + (pair ? best[i + 1] : 0.f);
       }
     }
@@ -2741,18 +2563,15 @@ void autotune_plan(df_ctx* c, Plan* pl, hipStream_t s) {
   // stage 2a: every surviving candidate, coarse (2 runs); 2b: the four best of each class again, among good neighbours and
   // with 6 runs -- the final choice between near-equal candidates used to flip from run to run (227 .. 234 steps/s for the
   // same build and box), a second, finer round takes most of that variance out
-  constexpr bool two_pass = true;
-  evaluate(rounds, two_pass ? 2 : reps);
-  if (two_pass) {
-    size_t keep = 0;
-    for (auto& kv : cands) {
-      std::vector<TuneCand>& v = kv.second;
-      std::sort(v.begin(), v.end(), [](const TuneCand& x, const TuneCand& y) { return x.situ_ms < y.situ_ms; });
-      if (v.size() > 4) v.resize(4);
-      keep = std::max(keep, v.size());
-    }
-    evaluate(keep, 6);
+  evaluate(rounds, 2);
+  size_t keep = 0;
+  for (auto& kv : cands) {
+    std::vector<TuneCand>& v = kv.second;
+    std::sort(v.begin(), v.end(), [](const TuneCand& x, const TuneCand& y) { return x.situ_ms < y.situ_ms; });
+    if (v.size() > 4) v.resize(4);
+    keep = std::max(keep, v.size());
   }
+  evaluate(keep, 6);
   apply(-1);
   if (getenv("DF_TUNE_LOG") && atoi(getenv("DF_TUNE_LOG"))) {      // tools: the candidates of every GEMM class, both stages
     for (auto& kv : cands) {
@@ -2762,46 +2581,28 @@ void autotune_plan(df_ctx* c, Plan* pl, hipStream_t s) {
     }
   }
   // stage 3: tile walk order of the chosen tile (GemmParams::gm), again timed inside the plan
-  constexpr bool tune_walk = true;
-  if (tune_walk) {
-    static const int gms[] = {0, 1, 2, 4, 8, 16};
-    constexpr int NG = sizeof(gms) / sizeof(gms[0]);
-    std::map<std::string, std::vector<double>> score;
-    for (int r = 0; r < NG; ++r) {
-      for (auto& o : pl->ops)
-        if (o.is_gemm && !o.c_ext) o.gp.gm = gms[r];
-      std::vector<float> best(pl->ops.size(), 1e30f);
-      for (int rep = 0; rep < reps + 1; ++rep) {
-        c->prof_on = true;
-        c->prof_used = 0;
-        c->prof_fam.clear();
-        c->prof_op.clear();
-        run_ops(c, pl, 0, pl->ops.size(), s, a);
-        c->prof_on = false;
-        HIPCHK(hipStreamSynchronize(s));
-        if (rep == 0) continue;
-        for (size_t i = 0; i < pl->ops.size(); ++i) {
-          float ms = 0;
-          HIPCHK(hipEventElapsedTime(&ms, c->prof_ev[2 * i], c->prof_ev[2 * i + 1]));
-          best[i] = std::min(best[i], ms);
-        }
-      }
-      for (size_t i = 0; i < pl->ops.size(); ++i) {
-        const Op& o = pl->ops[i];
-        if (!o.is_gemm || o.c_ext) continue;
-        std::vector<double>& v = score[tune_key(o)];
-        v.resize(NG, 0.0);
-        v[r] += best[i] + ((tune_pair && i + 1 < pl->ops.size() && !pl->ops[i + 1].is_gemm) ? best[i + 1] : 0.f);
-      }
-    }
-    for (auto& o : pl->ops) {
+  static const int gms[] = {0, 1, 2, 4, 8, 16};
+  constexpr int NG = sizeof(gms) / sizeof(gms[0]);
+  std::map<std::string, std::vector<double>> score;
+  for (int r = 0; r < NG; ++r) {
+    for (auto& o : pl->ops)
+      if (o.is_gemm && !o.c_ext) o.gp.gm = gms[r];
+    const std::vector<float> best = time_ops(3);
+    for (size_t i = 0; i < pl->ops.size(); ++i) {
+      const Op& o = pl->ops[i];
       if (!o.is_gemm || o.c_ext) continue;
-      const std::vector<double>& v = score[tune_key(o)];
-      int bi = 0;
-      for (int k = 1; k < NG; ++k)
-        if (v[k] < v[bi] * 0.99) bi = k;      // keep the default walk unless another is >1 % faster
-      o.gp.gm = gms[bi];
+      std::vector<double>& v = score[tune_key(o)];
+      v.resize(NG, 0.0);
+      v[r] += best[i] + ((i + 1 < pl->ops.size() && !pl->ops[i + 1].is_gemm) ? best[i + 1] : 0.f);
     }
+  }
+  for (auto& o : pl->ops) {
+    if (!o.is_gemm || o.c_ext) continue;
+    const std::vector<double>& v = score[tune_key(o)];
+    int bi = 0;
+    for (int k = 1; k < NG; ++k)
+      if (v[k] < v[bi] * 0.99) bi = k;      // keep the default walk unless another is >1 % faster
+    o.gp.gm = gms[bi];
   }
   c->prof_on = prof_was;
   c->prof_used = 0;
@@ -3081,7 +2882,7 @@ static Plan* unet_plan(df_ctx* c, int N, int H, int W, int T, bool cfg) {
   need_positive("unet", {{"batch", N}, {"H", H}, {"W", W}, {"context length", T}});
   if (H % (1 << (c->ucfg.n_mult - 1)) || W % (1 << (c->ucfg.n_mult - 1))) fail("latent %dx%d not divisible by the UNet downsampling", H, W);
   return get_plan(c, keyf("unet_%d_%d_%d_%d_%d", N, H, W, T, (int)cfg),
-                  [&](Plan* pl) { build_unet_like(c, pl, 0, N, H, W, T, cfg, false); });
+                  [&](Plan* pl) { build_unet_like(c, pl, 0, N, H, W, T, cfg); });
 }
 
 int df_unet_set_context(df_ctx* c, const float* context, int N, int T, void* stream) {
@@ -3264,7 +3065,7 @@ int df_classifier_forward(df_ctx* c, const float* x, const float* t, const float
     need_positive("classifier", {{"batch", B}, {"H", H}, {"W", W}, {"video frames", T}});
     cls_need_divisible(c, H, W);
     Plan* p = get_plan(c, keyf("cls_%d_%d_%d_%d", B, H, W, T),
-                       [&](Plan* pl) { build_unet_like(c, pl, 1, B, H, W, T, false, true); });
+                       [&](Plan* pl) { build_unet_like(c, pl, 1, B, H, W, T, false); });
     RunArgs a;
     a.x = x;
     a.t = t;
@@ -3929,12 +3730,9 @@ int df_test_scratch_read(void* host, int64_t bytes) {
   });
 }
 
-int df_test_linear_rows(const float* a, int lda, const float* tvals, int t_B, const uint16_t* W, const float* bias,
-                        float* out, int ldo, int M, int N, int K, int act, int lds_variant, void* stream) {
-  return guard([&] {
-    if (lds_variant) HIPCHK(launch_linear_rows_lds(a, lda, tvals, t_B, W, bias, out, ldo, M, N, K, act, (hipStream_t)stream));
-    else HIPCHK(launch_linear_rows(a, lda, W, bias, out, ldo, M, N, K, act, (hipStream_t)stream));
-  });
+int df_test_linear_rows(const float* a, int lda, const uint16_t* W, const float* bias, float* out, int ldo, int M, int N, int K,
+                        int act, void* stream) {
+  return guard([&] { HIPCHK(launch_linear_rows(a, lda, W, bias, out, ldo, M, N, K, act, (hipStream_t)stream)); });
 }
 
 // ONE block of the loaded UNet in isolation, against the reference's per-block tensors (golden G3): the plan builder's
@@ -3970,8 +3768,7 @@ int df_test_unet_block(df_ctx* c, const char* prefix, int kind, const float* x, 
       bf16_t* ctxb = b.buf<bf16_t>((size_t)N * T * Dc);
       const long n = (long)N * T * Dc;
       b.other("ctx.cast", [=](hipStream_t st, const RunArgs&) { return launch_cast_bf16(context, ctxb, n, st); });
-      constexpr bool no_lnfold = false;
-      if (!no_lnfold && Builder::px_ok(Cin, u.num_heads, T, H * W)) {     // same choice as build_unet_like
+      if (Builder::px_ok(Cin, u.num_heads, T, H * W)) {     // same choice as build_unet_like
         Builder::PX px = b.context_px(ctxb, N, T, Dc, p, Cin, u.num_heads);
         b.spatial_transformer(xin, dst, N, H * W, p, u.num_heads, nullptr, nullptr, T, ldvtc, &px);
       } else {
@@ -3982,9 +3779,8 @@ int df_test_unet_block(df_ctx* c, const char* prefix, int kind, const float* x, 
     } else {
       bf16_t* hb = b.cast2d(xin);
       const std::string wn = pre + p + (kind == 2 ? ".op" : ".conv");
-      const bool ups4 = kind == 3 && Cin % 64 == 0;   // as in the plan
-      GemmParams g = ups4 ? Builder::gp_conv3_ups4(hb, N, H, W, Cin, c->w_conv3_ups4(wn + ".weight", Cin), Cout)
-                          : Builder::gp_conv3(hb, N, H, W, Cin, c->w_conv3(wn + ".weight", Cin), Cout, kind == 2 ? 2 : 1, kind == 3 ? 1 : 0);
+      GemmParams g = kind == 3 ? Builder::gp_conv3_ups4(hb, N, H, W, Cin, c->w_conv3_ups4(wn + ".weight", Cin), Cout)   // as in the plan
+                               : Builder::gp_conv3(hb, N, H, W, Cin, c->w_conv3(wn + ".weight", Cin), Cout, kind == 2 ? 2 : 1, 0);
       Builder::out_f32(g, dst.p, Cout);
       g.bias = c->f32(wn + ".bias");
       b.gemm(g, 1, kind == 2 ? "down" : "up");

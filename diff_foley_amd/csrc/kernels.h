@@ -55,11 +55,6 @@ hipError_t launch_softmax_rows(const float* s, uint16_t* p, int rows, int T, int
 hipError_t launch_linear_rows(const float* a, int lda, const uint16_t* W, const float* bias, float* out, int ldo,
                               int M, int N, int K, int act_out /*0 none, 1 silu, 2 sigmoid*/, hipStream_t s);
 
-// Same, activations staged in LDS (weight stream is the only global traffic; HBM-rate).  tvals != nullptr: the
-// activations are the sinusoidal embedding (dim K) of tvals[m % t_B], generated in the kernel (`a` is ignored).
-hipError_t launch_linear_rows_lds(const float* a, int lda, const float* tvals, int t_B, const uint16_t* W,
-                                  const float* bias, float* out, int ldo, int M, int N, int K, int act_out, hipStream_t s);
-
 // Sinusoidal timestep embedding [cos | sin] (util.py:151-171), t fp32 (may be fractional) -> [N][dim] fp32
 hipError_t launch_timestep_embedding(const float* t, float* out, int N, int dim, hipStream_t s);
 

@@ -118,7 +118,7 @@ int df_unet_forward(df_ctx* ctx, const float* x_dev, const float* t_dev, float* 
                     void* stream);
 /* Classifier-free-guidance step of p_sample_ddim (ddim.py:241-245): runs the UNet on cat([x,x]) against the
  * 2B-row context set before ([uncond ; cond]) and returns e_u + scale*(e_c - e_u).  x, t, eps: B rows.  The ops in front of
- * the first cross-attention see identical rows in both halves and run on one half only (DF_NO_CFGDEDUP=1 disables). */
+ * the first cross-attention see identical rows in both halves and run on one half only. */
 int df_unet_forward_cfg(df_ctx* ctx, const float* x_dev, const float* t_dev, float* eps_out_dev, int B, int H, int W,
                         float guidance_scale, void* stream);
 /* Time embedding of a whole sample() call, hoisted out of the step loop like the context (timestep_embedding util.py:151-171 ->
@@ -274,11 +274,10 @@ int df_test_ln_chain(const uint16_t* A0_dev, const uint16_t* W0_dev, const float
                      const float* gamma_dev, const float* beta_dev, const float* W1_dev, const float* b1_dev,
                      float* t0_dev, void* y_dev, uint16_t* vt_dev, int M, int C, int N1, int mode, int T, int ldvt,
                      int tile0, int sk0, int tile1, int sk1, void* stream);
-/* Small-M weight-streaming linear (time-embedding path): lds_variant 1 = activations staged in LDS (tvals != NULL:
- * the activations are the sinusoidal embedding of tvals[m % t_B]); 0 = the register variant. */
-int df_test_linear_rows(const float* a_dev, int lda, const float* tvals_dev, int t_B, const uint16_t* W_dev,
-                        const float* bias_dev, float* out_dev, int ldo, int M, int N, int K, int act, int lds_variant,
-                        void* stream);
+/* Small-M weight-streaming linear (classifier head, classifier-gradient time MLP, CAVP head): out = act(a W^T + bias),
+ * act 0 none, 1 SiLU, 2 sigmoid. */
+int df_test_linear_rows(const float* a_dev, int lda, const uint16_t* W_dev, const float* bias_dev, float* out_dev, int ldo,
+                        int M, int N, int K, int act, void* stream);
 /* ONE block of the loaded UNet in isolation (checked against the reference's per-block tensors, golden G3): kind 0
  * ResBlock (openai_unetmodel.py:255-275; semb = SiLU(time_embed(t))), 1 SpatialTransformer (attention_openai.py:250-261),
  * 2 Downsample, 3 Upsample.  x [N*H*W][Cin] -> out [N*OH*OW][Cout], NHWC fp32; prefix e.g. "input_blocks.1.0". */

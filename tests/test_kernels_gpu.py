@@ -466,7 +466,8 @@ def test_fused_qkv_is_byte_reproducible_with_two_blocks_per_cu(tile1):
 
 @pytest.mark.parametrize("M,N,K,act", [(8, 1280, 320, 1), (8, 20160, 1280, 0), (16, 1280, 1280, 1), (2, 130, 256, 2),
                                        (3, 7, 64, 0)])
-def test_linear_rows_lds(M, N, K, act):
+def test_linear_rows(M, N, K, act):
+    """The small-M weight-streaming linear of the classifier head, the classifier-gradient time MLP and the CAVP head."""
     E = _eng()
     a = rnd((M, K), 50)
     w = bf(rnd((N, K), 51) / K ** 0.5)
@@ -475,31 +476,10 @@ def test_linear_rows_lds(M, N, K, act):
     ref = F.silu(ref) if act == 1 else (torch.sigmoid(ref) if act == 2 else ref)
     ac, wc, bc = a.cuda(), w.cuda(), b.cuda()
     out = torch.full((M, N), float("nan"), device="cuda")
-    rc = E.lib(PREC).df_test_linear_rows(ptr(ac), K, None, 0, ptr(wc), ptr(bc), ptr(out), N, M, N, K, act, 1, stream())
+    rc = E.lib(PREC).df_test_linear_rows(ptr(ac), K, ptr(wc), ptr(bc), ptr(out), N, M, N, K, act, stream())
     assert rc == 0, E.lib(PREC).df_last_error()
     torch.cuda.synchronize()
     assert rel_l2(out.cpu(), ref) < 1e-5
-
-
-def test_time_embed_first_layer_fused():
-    """[timestep embedding (util.py:151-171) with the CFG batch duplication] -> Linear -> SiLU in one launch."""
-    E = _eng()
-    B, K, N = 4, 320, 1280
-    t = torch.tensor([961.0, 37.5, 1.0, 500.25])
-    half = K // 2
-    freqs = torch.exp(-torch.log(torch.tensor(10000.0)) * torch.arange(half, dtype=torch.float32) / half)
-    ang = t[:, None] * freqs[None]
-    emb = torch.cat([torch.cos(ang), torch.sin(ang)], -1).repeat(2, 1)          # rows m -> t[m % B]
-    w = bf(rnd((N, K), 53) / K ** 0.5)
-    b = rnd((N,), 54)
-    ref = F.silu(emb @ w.float().t() + b)
-    tc, wc, bc = t.cuda(), w.cuda(), b.cuda()
-    out = torch.full((2 * B, N), float("nan"), device="cuda")
-    rc = E.lib(PREC).df_test_linear_rows(None, 0, ptr(tc), B, ptr(wc), ptr(bc), ptr(out), N, 2 * B, N, K, 1, 1, stream())
-    assert rc == 0, E.lib(PREC).df_last_error()
-    torch.cuda.synchronize()
-    assert (out.cpu() - ref).abs().max() < 2e-4       # cos/sin of arguments up to ~1e3 rad: fp32 argument reduction
-
 
 
 # ---- nearest-x2 upsample + conv3x3 as four 2x2-tap convs on the input-resolution map (csrc/gemm_m3.hip) ---------------------
