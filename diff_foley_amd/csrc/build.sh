@@ -18,7 +18,7 @@ for v in bf16 f16; do
   DEF=""; [ $v = f16 ] && DEF="-DDF_OPERAND_F16"
   for f in $SRCS; do
     o=build/$v/$f.o
-    if [ ! -f $o ] || [ $f.hip -nt $o ] || [ common.h -nt $o ] || [ gemm.h -nt $o ] || [ gemm_impl.h -nt $o ] || [ kernels.h -nt $o ] || [ ../../include/df_engine.h -nt $o ] || [ build.sh -nt $o ]; then
+    if [ ! -f $o ] || [ $f.hip -nt $o ] || [ common.h -nt $o ] || [ gemm.h -nt $o ] || [ gemm_tiles.def -nt $o ] || [ gemm_impl.h -nt $o ] || [ kernels.h -nt $o ] || [ ../../include/df_engine.h -nt $o ] || [ build.sh -nt $o ]; then
       hipcc $FLAGS $DEF -c $f.hip -o $o &
       pids+=($!)
     fi

@@ -495,7 +495,9 @@ inline int rup(int a, int b) { return cdiv(a, b) * b; }
 // ---------------------------------------------------------------------------------------------------------------
 // Tile / split-K choice: a small cost model in MFMA cycles (256 CUs, one 32x32x16 MFMA per 8 cycles per CU).
 void choose_tile(int M, int N, int K, int batch, bool geglu, int* tile, int* splitk) {
-  static const double eff[TILE_COUNT] = {1.0, 0.85, 0.85, 0.62, 0.55};
+  static const double eff[] = {1.0, 0.85, 0.85, 0.62, 0.55};      // the cost model knows the first five generic tiles
+  constexpr int TILE_COUNT = sizeof(eff) / sizeof(eff[0]);
+  static_assert(TILE_COUNT == TILE_32x128 + 1, "one efficiency per tile 128x128 .. 32x128");
   double best = 1e30;
   *tile = TILE_64x64;
   *splitk = 1;
@@ -3548,6 +3550,18 @@ int df_test_gemm_valid(const df_test_gemm_desc* d, int tile, int batch, int spli
     g_err = e.what();
     return -1;
   }
+}
+
+int df_test_gemm_tile_info(int tile, df_test_gemm_tile* out) {
+  std::lock_guard<std::recursive_mutex> hold(g_api_lock);
+  if (tile < 0 || tile >= TILE_ALL || !out || out->size != (int64_t)sizeof(df_test_gemm_tile)) {
+    g_err = "df_test_gemm_tile_info: no tile " + std::to_string(tile) + ", or a df_test_gemm_tile of another size";
+    return 1;
+  }
+  const GemmTileInfo& t = kGemmTiles[tile];
+  out->name = t.name; out->family = t.family; out->modes = t.modes;
+  out->bm = t.bm; out->bn = t.bn; out->dma_threads = gemm_halo_dma_threads(tile); out->ring = t.ring;
+  return 0;
 }
 
 int df_test_gemm_ex(const df_test_gemm_desc* d, void* stream) {

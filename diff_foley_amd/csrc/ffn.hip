@@ -369,11 +369,11 @@ bool pgeglu_valid(const GemmParams& p, int tile, int batch, int splitk) {
 }
 
 hipError_t launch_gemm_pgeglu(int tile_cfg, const GemmParams& p, hipStream_t stream) {
+#define DF_TILE_PGEGLU0(T, M0, M1, M2, M3, BM, BN, WGM, WGN, NST, PS, LNS)                                                    \
+  static_assert((BN) == 128 && (M0) && !(M1) && !(M2) && !(M3), "the persistent GEGLU kernel: 128 columns, linear only"); \
+  case T: return p.dbg ? launch_pgeglu<BM, WGM, WGN, NST, LNS, true>(p, stream) : launch_pgeglu<BM, WGM, WGN, NST, LNS, false>(p, stream);
   switch (tile_cfg) {
-    case TILE_PGEGLU_128: return p.dbg ? launch_pgeglu<128, 4, 1, 2, 10, true>(p, stream) : launch_pgeglu<128, 4, 1, 2, 10, false>(p, stream);
-    case TILE_PGEGLU_64: return p.dbg ? launch_pgeglu<64, 2, 2, 3, 20, true>(p, stream) : launch_pgeglu<64, 2, 2, 3, 20, false>(p, stream);
-    case TILE_PGEGLU_128_W8: return p.dbg ? launch_pgeglu<128, 4, 2, 2, 10, true>(p, stream) : launch_pgeglu<128, 4, 2, 2, 10, false>(p, stream);
-    case TILE_PGEGLU_128_W8L: return p.dbg ? launch_pgeglu<128, 4, 2, 2, 20, true>(p, stream) : launch_pgeglu<128, 4, 2, 2, 20, false>(p, stream);
+#include "gemm_tiles.def"
     default: return hipErrorInvalidValue;
   }
 }

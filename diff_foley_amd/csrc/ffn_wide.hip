@@ -346,10 +346,11 @@ bool wgeglu_valid(const GemmParams& p, int tile, int batch, int splitk) {
 }
 
 hipError_t launch_gemm_wgeglu(int tile_cfg, const GemmParams& p, hipStream_t stream) {
+#define DF_TILE_WGEGLU0(T, M0, M1, M2, M3, BM, BN, WGM, WGN, NST, PS, LNS)                                                           \
+  static_assert((BN) == 320 && (BM) % 64 == 0 && (WGM) == 4 && (WGN) == 2 && (M0) && !(M1) && !(M2) && !(M3), "the wide GEGLU kernel"); \
+  case T: return p.dbg ? launch_wgeglu<(BM) / 64, NST, true>(p, stream) : launch_wgeglu<(BM) / 64, NST, false>(p, stream);
   switch (tile_cfg) {
-    case TILE_WGEGLU_256: return p.dbg ? launch_wgeglu<4, 2, true>(p, stream) : launch_wgeglu<4, 2, false>(p, stream);
-    case TILE_WGEGLU_128: return p.dbg ? launch_wgeglu<2, 2, true>(p, stream) : launch_wgeglu<2, 2, false>(p, stream);
-    case TILE_WGEGLU_64: return p.dbg ? launch_wgeglu<1, 3, true>(p, stream) : launch_wgeglu<1, 3, false>(p, stream);
+#include "gemm_tiles.def"
     default: return hipErrorInvalidValue;
   }
 }

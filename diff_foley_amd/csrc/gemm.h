@@ -84,75 +84,53 @@ __device__ __forceinline__ DfTouch gemm_kernarg_touch() { return df_entry_touch(
 __device__ __forceinline__ void gemm_kernarg_touch_end(const DfTouch& v) { df_entry_touch_end(v); }
 #endif
 
+// The tiles: gemm_tiles.def has one row per tile id; the enum and every look-up below are generated from it.
+enum GemmTileFamily { DF_FAM_GEN = 0, DF_FAM_HALO = 1, DF_FAM_PS = 2, DF_FAM_PGEGLU = 3, DF_FAM_WGEGLU = 4, DF_FAM_RETIRED = 5 };
 enum GemmTile {
-  TILE_128x128 = 0, TILE_128x64 = 1, TILE_64x128 = 2, TILE_64x64 = 3, TILE_32x128 = 4, TILE_COUNT = 5,   // generic
-  // conv3x3 stride-1 kernels with an LDS-staged halo tile (BM output pixels = patches of th x tw, BN couts)
-  TILE_HALO_128x64 = 5, TILE_HALO_256x64 = 6, TILE_HALO_128x128 = 7,
-  // generic kernel with 8 wavefronts (512 threads): high arithmetic intensity per LDS byte, for split-K streaming
-  TILE_128x256 = 8, TILE_256x128 = 9,
-  // generic kernel, double-buffered (ring depth 2): less LDS -> 2-5 resident blocks per CU, for short-K layers
-  TILE_128x128_S = 10, TILE_128x64_S = 11, TILE_64x128_S = 12, TILE_64x64_S = 13, TILE_32x128_S = 14,
-  // halo kernels with an 8-deep weight ring: more weight bytes in flight per CU for the weight-streaming layers
-  TILE_HALO_128x64_D = 15, TILE_HALO_256x64_D = 16,
-  // 192 output pixels (three 4x16 patches) x 64 couts, 4 wavefronts of 96x32: (8192, 320) becomes 43 x 5 = 215 blocks on 256 CUs
-  // where the 256x64 tile gives 160 (the model's channel counts are 5 * 2^k: power-of-two tiles leave 3/8 of the CUs idle)
-  TILE_HALO_192x64 = 17,
-  // PRODUCER-SPECIALISED generic tiles (round 4; gemm_impl.h PS): 4 consumer wavefronts (2 x 2) run the MFMAs, 4 producer
-  // wavefronts issue the LDS-DMA requests of the ring -- 8 wavefronts, one of each role per SIMD.  (ids 18-20 were the deep
-  // weight-ring tiles of an earlier round-4 experiment: experiments/deep_weight_ring_tiles.md; never built into the product.)
-  TILE_PS_256x128 = 18, TILE_PS_128x128 = 19, TILE_PS2_128x128 = 20,      // PS2: 8 producer wavefronts (12 in the block)
-  // persistent LayerNorm-folded GEGLU projection (ffn.hip): 2 resident blocks per CU walk a tile queue, one continuous operand
-  // stream across tiles, epilogue out of the accumulator registers.  128 x 128 tiles (C <= 640) / 64 x 128 tiles.
-  TILE_PGEGLU_128 = 21, TILE_PGEGLU_64 = 22,
-  // producer-specialised halo conv tiles: 4 consumer + 4 producer wavefronts.  (8 producers -- 12 wavefronts, 168 VGPRs each --
-  // spill in the tap loop: 32 us against 21.8 us on the 320 -> 320 conv at 16 x 64; measured and not kept.)
-  TILE_HALO_PS_192x64 = 23, TILE_HALO_PS_128x64 = 24, TILE_HALO_PS_128x128 = 25,
-  // producer-specialised small generic tiles (the transformer's K = 320 .. 1280 projections: 160 blocks on 256 CUs, one block per
-  // CU, no second block to overlap with): 4 + 4 and 4 + 8 wavefronts
-  TILE_PS_64x64 = 26, TILE_PS2_64x64 = 27, TILE_PS_128x64 = 28, TILE_PS_64x128 = 29,
-  // persistent GEGLU projection with EIGHT wavefronts per block (4 x 2, each 32 rows x 64 columns; round 5): a wavefront issues
-  // in order -- its LDS-DMA requests (~130 cycles each), its MFMAs and its GELU arithmetic are one serial stream (1.8 k cycles per
-  // K step for 512 of MFMA, 6.5 k of epilogue arithmetic per tile in the 4-wavefront form, whatever the co-resident block does:
-  // the DF_PG_STAGGER experiment).  Twice the wavefronts halve every one of those streams.  31: 20 row-statistics slots (C = 1280)
-  TILE_PGEGLU_128_W8 = 30, TILE_PGEGLU_128_W8L = 31,
-  // WIDE GEGLU tiles (ffn_wide.hip, round 6): BM x 320 output columns (5 * 2^6: the model's channel counts are 5 * 2^k, so N = 8C
-  // is always a multiple of 320 and (8192, 2560) / (2048, 5120) / (512, 10240) are EXACTLY 256 tiles of 256 / 128 / 64 rows -- one
-  // per CU, no second round), 8 wavefronts as 4 (M) x 2 (N) on v_mfma_f32_16x16x32 fragments (80-column x / gate halves), two per
-  // SIMD, one whole K panel per block, epilogue out of the accumulators.  Half the L2 -> LDS bytes per FLOP of the 128 x 128 tiles.
-  TILE_WGEGLU_256 = 32, TILE_WGEGLU_128 = 33, TILE_WGEGLU_64 = 34, TILE_ALL = 35
+#define DF_TILE(ID, NAME, ...) NAME,
+#include "gemm_tiles.def"
+#undef DF_TILE
+  TILE_ALL
 };
-static inline bool gemm_tile_is_pgeglu(int cfg) { return cfg == TILE_PGEGLU_128 || cfg == TILE_PGEGLU_64 || cfg == TILE_PGEGLU_128_W8 || cfg == TILE_PGEGLU_128_W8L; }
-static inline bool gemm_tile_is_wgeglu(int cfg) { return cfg >= TILE_WGEGLU_256 && cfg <= TILE_WGEGLU_64; }
-static inline bool gemm_tile_is_ps(int cfg) { return (cfg >= TILE_PS_256x128 && cfg <= TILE_PS2_128x128) || (cfg >= TILE_PS_64x64 && cfg <= TILE_PS_64x128); }
-// ring depths (activation ring, weight ring) of the generic tiles; 0 for halo tiles
-static inline void gemm_tile_rings(int cfg, int* nsta, int* nstb) {
-  static const int a[TILE_ALL] = {4, 5, 5, 4, 4, 0, 0, 0, 3, 3, 2, 2, 2, 2, 2, 0, 0, 0, 3, 4, 4, 2, 3, 0, 0, 0, 4, 4, 4, 4, 2, 2, 2, 2, 3};
-  static const int b[TILE_ALL] = {4, 5, 5, 4, 4, 0, 0, 0, 3, 3, 2, 2, 2, 2, 2, 0, 0, 0, 3, 4, 4, 2, 3, 0, 0, 0, 4, 4, 4, 4, 2, 2, 2, 2, 3};
-  *nsta = a[cfg];
-  *nstb = b[cfg];
-}
+struct GemmTileInfo {
+  const char* name;      // display name (tools)
+  int family, part;      // GemmTileFamily; which of the family's two translation units holds it
+  int modes;             // bit m: instantiated for MODE m
+  int bm, bn, wgm, wgn, ring, ps, lns;
+};
+inline constexpr GemmTileInfo kGemmTiles[TILE_ALL] = {
+#define DF_TILE(ID, NAME, DISP, FAM, PART, M0, M1, M2, M3, BM, BN, WGM, WGN, RING, PS, LNS) \
+  {DISP, DF_FAM_##FAM, PART, (M0) | (M1) << 1 | (M2) << 2 | (M3) << 3, BM, BN, WGM, WGN, RING, PS, LNS},
+#include "gemm_tiles.def"
+#undef DF_TILE
+};
+#define DF_TILE(ID, NAME, ...) static_assert(NAME == ID, "gemm_tiles.def: a tile id is its row's position (the ids are a file format)");
+#include "gemm_tiles.def"
+#undef DF_TILE
+
+// Any int may be asked about; an id outside the table is of no family and no MODE.
+static inline int gemm_tile_family(int cfg) { return (cfg >= 0 && cfg < TILE_ALL) ? kGemmTiles[cfg].family : -1; }
+static inline bool gemm_tile_is_halo(int cfg) { return gemm_tile_family(cfg) == DF_FAM_HALO; }
+static inline bool gemm_tile_is_ps(int cfg) { return gemm_tile_family(cfg) == DF_FAM_PS; }
+static inline bool gemm_tile_is_pgeglu(int cfg) { return gemm_tile_family(cfg) == DF_FAM_PGEGLU; }
+static inline bool gemm_tile_is_wgeglu(int cfg) { return gemm_tile_family(cfg) == DF_FAM_WGEGLU; }
+static inline bool gemm_tile_has_mode(int cfg, int mode) { return cfg >= 0 && cfg < TILE_ALL && ((kGemmTiles[cfg].modes >> mode) & 1); }
+// MODE 0: linear / 1x1;  1: 3x3 stride 1 (tap offsets are linear, 2 VALU per request);  2: 3x3 stride 2 / upsampled;
+// 3: phase-decomposed upsample conv (taps == 4)
+static inline int gemm_mode(const GemmParams& p) { return (p.taps == 4) ? 3 : (p.taps != 9) ? 0 : ((p.stride == 1 && !p.ups) ? 1 : 2); }
 // 64-column slots of row statistics a LayerNorm-folded GEMM can fold per row (gemm_impl.h LNS): C <= 1280
 static inline int gemm_ln_max_slots() { return 20; }
 
-static inline bool gemm_tile_is_halo(int cfg) {
-  return (cfg >= TILE_HALO_128x64 && cfg <= TILE_HALO_128x128) || cfg == TILE_HALO_128x64_D || cfg == TILE_HALO_256x64_D ||
-         cfg == TILE_HALO_192x64 || (cfg >= TILE_HALO_PS_192x64 && cfg <= TILE_HALO_PS_128x128);
-}
+// The look-ups below take an id of the table.
 // threads of a halo tile that issue its DMA requests (the LDS staging geometry follows from them: 8 threads per 128-B row)
 static inline int gemm_halo_dma_threads(int cfg) {
-  return (cfg == TILE_HALO_256x64 || cfg == TILE_HALO_256x64_D) ? 512 : 256;
+  const GemmTileInfo& t = kGemmTiles[cfg];
+  return 64 * t.wgm * t.wgn * (t.ps ? t.ps : 1);
 }
-static inline int gemm_halo_ring(int cfg) { return (cfg == TILE_HALO_128x64_D || cfg == TILE_HALO_256x64_D) ? 8 : 4; }
-
+static inline int gemm_halo_ring(int cfg) { return kGemmTiles[cfg].ring; }     // weight ring depth
 static inline void gemm_tile_dims(int cfg, int* bm, int* bn) {
-  static const int d[TILE_ALL][2] = {{128, 128}, {128, 64}, {64, 128}, {64, 64}, {32, 128},
-                                     {128, 64},  {256, 64}, {128, 128}, {128, 256}, {256, 128},
-                                     {128, 128}, {128, 64}, {64, 128}, {64, 64}, {32, 128},
-                                     {128, 64}, {256, 64}, {192, 64}, {256, 128}, {128, 128}, {128, 128}, {128, 128}, {64, 128},
-                                     {192, 64}, {128, 64}, {128, 128}, {64, 64}, {64, 64}, {128, 64}, {64, 128}, {128, 128}, {128, 128},
-                                     {256, 320}, {128, 320}, {64, 320}};
-  *bm = d[cfg][0];
-  *bn = d[cfg][1];
+  *bm = kGemmTiles[cfg].bm;
+  *bn = kGemmTiles[cfg].bn;
 }
 
 // Can (tile, batch, splitk) run this problem?  (halo tiles: 3x3 stride-1 convs whose patch geometry fits LDS)

@@ -161,16 +161,14 @@ __global__ __launch_bounds__(256) void splitk_reduce_vec_kernel(GemmParams p) {
 bool gemm_tile_valid(const GemmParams& p, int tile, int batch, int splitk) {
   const int nk = p.K / 64;
   if (p.taps == 4) {     // phase-decomposed upsample conv (MODE 3): a subset of the generic tiles, plain epilogues only
-    static const bool ok3[TILE_ALL] = {false, false, false, true, false, false, false, false, true, true, true, true, true, true, false, false, false, false,
-                                       false, false, false, false, false, false, false, false, false, false, false, false, false, false, false, false, false};     // (no producer-specialised MODE 3 instantiation)
-    if (tile < 0 || tile >= TILE_ALL || !ok3[tile] || batch > 1) return false;
+    if (!gemm_tile_has_mode(tile, 3) || batch > 1) return false;
     if (p.geglu || p.vt || p.ln_stats || p.stats || p.w_rows > 0 || p.sm_w > 0 || p.Cin2 > 0 || p.res || p.store_nchw) return false;
     if (splitk > 1 && (p.N & 3) != 0) return false;
     return splitk == 1 || nk / splitk >= 2;
   }
   if (gemm_tile_is_pgeglu(tile)) return pgeglu_valid(p, tile, batch, splitk);
   if (gemm_tile_is_wgeglu(tile)) return wgeglu_valid(p, tile, batch, splitk);
-  if (gemm_tile_is_ps(tile) && p.taps == 9 && (p.stride != 1 || p.ups)) return false;     // instantiated for MODE 0 and 1
+  if (!gemm_tile_has_mode(tile, gemm_mode(p))) return false;     // no such instantiation (gemm_tiles.def M0 .. M3), or no such tile
   if (!gemm_tile_is_halo(tile)) {
     if (tile < 0 || tile >= TILE_ALL) return false;
     if (p.geglu && ((p.N & 63) != 0 || (p.ldc & 3) != 0)) return false;   // GEGLU needs the vectorised block epilogue
@@ -247,15 +245,14 @@ hipError_t launch_gemm(const GemmParams& p, int tile_cfg, int batch, hipStream_t
   if (epi == EPI_LNC && (!p.ln_stats || p.aux)) return hipErrorInvalidValue;
   if (epi == EPI_XS && (!p.ln_stats || p.taps != 1 || !vec || (p.N & 63) != 0)) return hipErrorInvalidValue;
   hipError_t e;
-  // MODE 0: linear / 1x1;  1: 3x3 stride 1 (tap offsets are linear, 2 VALU per request);  2: 3x3 stride 2 / upsampled
-  const int mode = (p.taps == 4) ? 3 : (p.taps != 9) ? 0 : ((p.stride == 1 && !p.ups) ? 1 : 2);
+  const int mode = gemm_mode(p), part = (tile_cfg >= 0 && tile_cfg < TILE_ALL) ? kGemmTiles[tile_cfg].part : 0;
   if (mode == 3) {
     if (batch > 1 || gemm_tile_is_halo(tile_cfg) || p.OH != p.H || p.OW != p.Wd || p.K != 4 * p.Cin || p.w_bs != (long)p.N * p.K)
       return hipErrorInvalidValue;
     e = launch_gemm_m3(tile_cfg, epi, p, zdim, stream);
   } else if (gemm_tile_is_halo(tile_cfg)) e = launch_gemm_halo(tile_cfg, epi, p, zdim, stream);
-  else if (gemm_tile_is_ps(tile_cfg)) e = (tile_cfg >= TILE_PS_64x64) ? launch_gemm_ps_small(mode, tile_cfg, epi, p, zdim, stream) : launch_gemm_ps(mode, tile_cfg, epi, p, zdim, stream);
-  else if (mode == 0) e = (tile_cfg <= TILE_256x128) ? launch_gemm_m0a(tile_cfg, epi, p, zdim, stream) : launch_gemm_m0b(tile_cfg, epi, p, zdim, stream);
+  else if (gemm_tile_is_ps(tile_cfg)) e = part ? launch_gemm_ps_small(mode, tile_cfg, epi, p, zdim, stream) : launch_gemm_ps(mode, tile_cfg, epi, p, zdim, stream);
+  else if (mode == 0) e = part ? launch_gemm_m0b(tile_cfg, epi, p, zdim, stream) : launch_gemm_m0a(tile_cfg, epi, p, zdim, stream);
   else if (mode == 1) e = launch_gemm_m1(tile_cfg, epi, p, zdim, stream);
   else e = launch_gemm_m2(tile_cfg, epi, p, zdim, stream);
   if (e != hipSuccess) return e;

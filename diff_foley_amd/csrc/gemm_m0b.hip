@@ -1,4 +1,5 @@
-// Instantiations of the implicit-GEMM kernel (gemm_impl.h), MODE 0: one translation unit per mode so they build in parallel.
+// Instantiations of the implicit-GEMM kernel (gemm_impl.h), MODE 0: the GEN rows of gemm_tiles.def, part 1.  One translation unit per
+// mode (MODE 0: two) so they build in parallel.
 #include "gemm_impl.h"
 
 hipError_t launch_gemm_m0b(int tile_cfg, int epi, const GemmParams& p, int zdim, hipStream_t stream) {
@@ -14,12 +15,9 @@ hipError_t launch_gemm_m0b(int tile_cfg, int epi, const GemmParams& p, int zdim,
       case EPI_XS: return launch_cfg<BM, BN, WGM, WGN, NST, 0, EPI_XS>(p, zdim, stream); \
       default: return hipErrorInvalidValue;                              \
     }
+#define DF_TILE_GEN1(T, M0, M1, M2, M3, BM, BN, WGM, WGN, NST, PS, LNS) DF_TILE_IF_##M0(DF_T(T, BM, BN, WGM, WGN, NST))
   switch (tile_cfg) {
-    DF_T(TILE_128x128_S, 128, 128, 2, 2, 2)
-    DF_T(TILE_128x64_S, 128, 64, 2, 2, 2)
-    DF_T(TILE_64x128_S, 64, 128, 2, 2, 2)
-    DF_T(TILE_64x64_S, 64, 64, 2, 2, 2)
-    DF_T(TILE_32x128_S, 32, 128, 1, 4, 2)
+#include "gemm_tiles.def"
     default: return hipErrorInvalidValue;
   }
 #undef DF_T

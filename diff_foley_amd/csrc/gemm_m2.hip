@@ -1,4 +1,5 @@
-// Instantiations of the implicit-GEMM kernel (gemm_impl.h), MODE 2: one translation unit per mode so they build in parallel.
+// Instantiations of the implicit-GEMM kernel (gemm_impl.h), MODE 2: the GEN rows of gemm_tiles.def that have M2.  One translation
+// unit per mode (MODE 0: two) so they build in parallel.
 #include "gemm_impl.h"
 
 hipError_t launch_gemm_m2(int tile_cfg, int epi, const GemmParams& p, int zdim, hipStream_t stream) {
@@ -10,19 +11,10 @@ hipError_t launch_gemm_m2(int tile_cfg, int epi, const GemmParams& p, int zdim, 
       case EPI_ANY: return launch_cfg<BM, BN, WGM, WGN, NST, 2, EPI_ANY>(p, zdim, stream); \
       default: return hipErrorInvalidValue;                              \
     }
+#define DF_TILE_GEN0(T, M0, M1, M2, M3, BM, BN, WGM, WGN, NST, PS, LNS) DF_TILE_IF_##M2(DF_T(T, BM, BN, WGM, WGN, NST))
+#define DF_TILE_GEN1(T, M0, M1, M2, M3, BM, BN, WGM, WGN, NST, PS, LNS) DF_TILE_IF_##M2(DF_T(T, BM, BN, WGM, WGN, NST))
   switch (tile_cfg) {
-    DF_T(TILE_128x128, 128, 128, 2, 2, 4)
-    DF_T(TILE_128x64, 128, 64, 2, 2, 5)
-    DF_T(TILE_64x128, 64, 128, 2, 2, 5)
-    DF_T(TILE_64x64, 64, 64, 2, 2, 4)
-    DF_T(TILE_32x128, 32, 128, 1, 4, 4)
-    DF_T(TILE_128x256, 128, 256, 2, 4, 3)
-    DF_T(TILE_256x128, 256, 128, 4, 2, 3)
-    DF_T(TILE_128x128_S, 128, 128, 2, 2, 2)
-    DF_T(TILE_128x64_S, 128, 64, 2, 2, 2)
-    DF_T(TILE_64x128_S, 64, 128, 2, 2, 2)
-    DF_T(TILE_64x64_S, 64, 64, 2, 2, 2)
-    DF_T(TILE_32x128_S, 32, 128, 1, 4, 2)
+#include "gemm_tiles.def"
     default: return hipErrorInvalidValue;
   }
 #undef DF_T

@@ -46,6 +46,24 @@ class GemmDesc(C.Structure):
         super().__init__(size=C.sizeof(GemmDesc), **kw)
 
 
+class GemmTile(C.Structure):
+    """include/df_engine.h df_test_gemm_tile: one row of the GEMM tile table (csrc/gemm_tiles.def)."""
+    _fields_ = [("size", C.c_int64), ("name", C.c_char_p)] + [(n, C.c_int) for n in ("family", "bm", "bn", "dma_threads", "ring", "modes")]
+
+
+TILE_FAMILIES = ("generic", "halo", "ps", "pgeglu", "wgeglu", "retired")      # df_test_gemm_tile.family
+
+
+def gemm_tiles(L=None):
+    """The tile table of a loaded build (host only): {id: dict(name, family, bm, bn, dma_threads, ring, modes)}."""
+    L = L or lib()
+    out, t = {}, GemmTile(size=C.sizeof(GemmTile))
+    while L.df_test_gemm_tile_info(len(out), C.byref(t)) == 0:
+        out[len(out)] = dict(name=t.name.decode(), family=TILE_FAMILIES[t.family], bm=t.bm, bn=t.bn, dma_threads=t.dma_threads,
+                             ring=t.ring, modes=tuple(m for m in range(4) if t.modes >> m & 1))
+    return out
+
+
 class UNetConfig(C.Structure):
     _fields_ = [("in_channels", C.c_int), ("out_channels", C.c_int), ("model_channels", C.c_int),
                 ("num_res_blocks", C.c_int), ("channel_mult", C.c_int * 8), ("n_mult", C.c_int),
@@ -163,6 +181,7 @@ _SIGS = {
     "df_test_conv3x3_bwd_data": [C.c_void_p] * 5 + [C.c_int] * 8 + [C.c_void_p],
     "df_test_gemm_ex": [C.POINTER(GemmDesc), C.c_void_p],
     "df_test_gemm_valid": [C.POINTER(GemmDesc), C.c_int, C.c_int, C.c_int],
+    "df_test_gemm_tile_info": [C.c_int, C.POINTER(GemmTile)],
     "df_test_xattn_chain": [C.c_void_p] * 10 + [C.c_int] * 6 + [C.c_void_p] * 10 + [C.c_int, C.c_int, C.c_void_p],
     "df_test_pack_ffproj": [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p],
     "df_test_peak": [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p],

@@ -357,6 +357,17 @@ typedef struct df_test_gemm_desc {
 int df_test_gemm_ex(const df_test_gemm_desc* d, void* stream);
 /* gemm_tile_valid(d, tile, batch, splitk): 1 / 0, or -1 (message in df_last_error) for a malformed descriptor.  Host only. */
 int df_test_gemm_valid(const df_test_gemm_desc* d, int tile, int batch, int splitk);
+/* Row `tile` of the GEMM tile table (csrc/gemm_tiles.def): what a tile id of the plan tables and tune caches means.  `size` must be
+ * sizeof(df_test_gemm_tile).  family: 0 generic, 1 halo conv, 2 producer-specialised, 3 persistent GEGLU, 4 wide GEGLU, 5 retired
+ * (id reserved, never valid).  dma_threads: the threads that issue DMA requests; ring: depth of the LDS operand rings (halo: of the
+ * weight ring); modes: bit m set = built for MODE m (0 linear, 1 conv s1, 2 conv s2 / upsampled, 3 phase-upsample).  Returns
+ * non-zero for an id outside the table (ids are 0 .. count-1 without gaps).  Host only. */
+typedef struct df_test_gemm_tile {
+  int64_t size;
+  const char* name;
+  int family, bm, bn, dma_threads, ring, modes;
+} df_test_gemm_tile;
+int df_test_gemm_tile_info(int tile, df_test_gemm_tile* out);
 /* The folded cross-attention of one SpatialTransformer (engine.hip context_px, st.xs, st.xo), every intermediate out: ctx [NB*Tc][Dc]
  * and Wkv [2C][Dc] (to_k | to_v) operand type; Wq [C][C], gamma (norm2), bq = Wq . beta fp32; Wo [C][C] operand, bo fp32; x fp32
  * [NB*T][C], xb its operand copy, xstats float2 [NB*T][C/64] (sum, sum of squares per 64 columns).  Outputs: kv [NB*Tc][2C],

@@ -71,6 +71,65 @@ def test_gemm_desc_binding_matches_the_build():
         assert b"descriptor" in L.df_last_error()
 
 
+# What a GEMM tile id means: the ids are written into the shipped plan tables (diff_foley_amd/tuned/) and into every tune-cache file,
+# so they are a file format.  (display name, family, BM, BN) per id, restated here independently of csrc/gemm_tiles.def.
+_TILE_TABLE = {
+    0: ("128x128", "generic", 128, 128), 1: ("128x64", "generic", 128, 64), 2: ("64x128", "generic", 64, 128),
+    3: ("64x64", "generic", 64, 64), 4: ("32x128", "generic", 32, 128),
+    5: ("H128x64", "halo", 128, 64), 6: ("H256x64", "halo", 256, 64), 7: ("H128x128", "halo", 128, 128),
+    8: ("128x256", "generic", 128, 256), 9: ("256x128", "generic", 256, 128),
+    10: ("128x128s", "generic", 128, 128), 11: ("128x64s", "generic", 128, 64), 12: ("64x128s", "generic", 64, 128),
+    13: ("64x64s", "generic", 64, 64), 14: ("32x128s", "generic", 32, 128),
+    15: ("H128x64d", "halo", 128, 64),
+    16: ("H256x64d", "retired", 256, 64),      # no feature map ever fitted its LDS budget (csrc/gemm_tiles.def); the id stays reserved
+    17: ("H192x64", "halo", 192, 64),
+    18: ("P256x128", "ps", 256, 128), 19: ("P128x128", "ps", 128, 128), 20: ("P2_128x128", "ps", 128, 128),
+    21: ("P128", "pgeglu", 128, 128), 22: ("P64", "pgeglu", 64, 128),
+    23: ("HP192x64", "halo", 192, 64), 24: ("HP128x64", "halo", 128, 64), 25: ("HP128x128", "halo", 128, 128),
+    26: ("P64x64", "ps", 64, 64), 27: ("P2_64x64", "ps", 64, 64), 28: ("P128x64", "ps", 128, 64), 29: ("P64x128", "ps", 64, 128),
+    30: ("P128w8", "pgeglu", 128, 128), 31: ("P128w8L", "pgeglu", 128, 128),
+    32: ("W256", "wgeglu", 256, 320), 33: ("W128", "wgeglu", 128, 320), 34: ("W64", "wgeglu", 64, 320),
+}
+_TILE_RETIRED = {16: (512, 8)}      # (DMA threads, weight ring) of a retired halo id that the GPU tests' literal lists still name
+
+
+def test_gemm_tile_table_is_pinned():
+    """df_test_gemm_tile_info answers on the host, on both builds, with the 35 rows written out above, and refuses ids outside the
+    table.  The literal tile lists the GPU tests keep (an independent restatement there) equal what the table says: generic +
+    producer-specialised ids, halo ids with their (BM, BN, DMA threads, weight ring), the generic ids that take MODE 2, the row
+    count.  A retired id stays in the halo lists of the GPU tests (they skip a pair the library refuses); the table must refuse it."""
+    import ctypes as C
+    import test_backward_kernels_gpu as TB
+    import test_gemm_epilogues_gpu as TG
+    import test_kernels_gpu as TK
+    for prec in ("bf16", "fp16"):
+        L = E.lib(prec)
+        tiles = E.gemm_tiles(L)
+        assert {t: (r["name"], r["family"], r["bm"], r["bn"]) for t, r in tiles.items()} == _TILE_TABLE
+        info = E.GemmTile(size=C.sizeof(E.GemmTile))
+        for bad in (-1, len(_TILE_TABLE), 1 << 20):
+            assert L.df_test_gemm_tile_info(bad, C.byref(info)) != 0
+        info.size -= 8
+        assert L.df_test_gemm_tile_info(0, C.byref(info)) != 0
+        fam = lambda *names: [t for t, r in tiles.items() if r["family"] in names]
+        assert TG.TILE_ALL == len(tiles)
+        assert TK.TILES == fam("generic", "ps")
+        assert TB._TILES_S2 == [t for t in fam("generic") if 2 in tiles[t]["modes"]] == fam("generic")
+        halo = {t: (r["bm"], r["bn"], r["dma_threads"], r["ring"]) for t, r in tiles.items() if r["family"] == "halo"}
+        for t, geo in _TILE_RETIRED.items():
+            assert tiles[t]["family"] == "retired" and tiles[t]["modes"] == ()
+            halo[t] = (tiles[t]["bm"], tiles[t]["bn"]) + geo
+        assert TK._HALO_GEO == halo and list(TK.HALO) == sorted(halo)
+        # a retired id is refused for every problem: the conv every live halo tile accepts, and a plain linear
+        conv = E.GemmDesc(conv=1, NB=2, H=16, Wd=64, Cin=64, N=64, stride=1)
+        lin = E.GemmDesc(M=256, N=128, K=256)
+        for t, r in tiles.items():
+            if r["family"] == "halo":
+                assert r["modes"] == (1,) and L.df_test_gemm_valid(C.byref(conv), t, 1, 1) == 1
+            if r["family"] == "retired":
+                assert L.df_test_gemm_valid(C.byref(conv), t, 1, 1) == 0 and L.df_test_gemm_valid(C.byref(lin), t, 1, 1) == 0
+
+
 def test_no_gpu_fails_loudly():
     if torch.cuda.is_available():
         pytest.skip("GPU present")

@@ -11,7 +11,8 @@ from test_kernels_gpu import rnd, bf, ptr, stream
 K.PREC = os.environ.get("DF_PRECISION", "bf16")
 E = K._eng(); L = E.lib(K.PREC); odt = K.odt()
 reps = int(sys.argv[1]) if len(sys.argv) > 1 else 16
-TILES = [int(x) for x in os.environ.get("TILES", "0,1,2,3,4,8,9,10,11,12,13,14,18,19,20,26,27,28,29").split(",")]
+TILES = ([int(x) for x in os.environ["TILES"].split(",")] if os.environ.get("TILES") else
+         [t for t, r in E.gemm_tiles(L).items() if r["family"] in ("generic", "ps")])      # every tile of the generic kernel
 bad = []
 for (M, C, T) in ((8192, 320, 1024), (2048, 640, 256), (512, 1280, 64)):
     A0 = bf(rnd((M, C), 40)).to(odt).cuda(); W0 = bf(rnd((C, C), 41) / C ** 0.5).to(odt).cuda()

@@ -10,13 +10,14 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import diff_foley_amd  # noqa
 from diff_foley_amd import engine as E
-from gemm_bench import ptr, TILES
+from gemm_bench import ptr, TILES, ALL_TILES
 
 L = E.lib()
 st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+WIDE = tuple(t for t, r in ALL_TILES.items() if r["family"] == "wgeglu")
+PG = tuple(t for t, r in ALL_TILES.items() if r["family"] == "pgeglu") + WIDE
 TILES = dict(TILES)
-TILES.update({21: "P128", 22: "P64", 30: "P128w8", 31: "P128w8L", 32: "W256", 33: "W128", 34: "W64"})
-PG = (21, 22, 30, 31, 32, 33, 34)
+TILES.update({t: ALL_TILES[t]["name"] for t in PG})
 SWITCHES = [0, 8, 6, 15, 31, 47, 63] if len(sys.argv) > 2 else [0]      # second argument: also the debug switches
 tiles = [int(x) for x in sys.argv[1].split(",")] if len(sys.argv) > 1 else [8, 9, 10, 11, 12, 13, 18, 21, 22, 30, 31, 32, 33, 34]
 for (M, K) in ((8192, 320), (2048, 640), (512, 1280)):
@@ -31,7 +32,7 @@ for (M, K) in ((8192, 320), (2048, 640), (512, 1280)):
     line = []
     for t in tiles:
         for dbg in ([0] if t not in PG else SWITCHES):
-            wide = t in (32, 33, 34)      # wide tiles: ONE weight buffer (the test entry keeps its 320-column packing: dbg bit 7), warm
+            wide = t in WIDE      # wide tiles: ONE weight buffer (the test entry keeps its 320-column packing: dbg bit 7), warm
             call = lambda i: L.df_test_geglu(ptr(a), ptr(ws[0 if wide else i % nbuf]), ptr(stats), ptr(cs), ptr(bias), ptr(out), M, K, N1, t,
                                              dbg | (128 if wide else 0), st)
             if call(0) != 0:
