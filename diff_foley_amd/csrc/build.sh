@@ -11,14 +11,16 @@ cd "$(dirname "$0")"
 # family -- not the GEMMs, whose one argument is a struct) get them in SGPRs at wavefront launch instead of through s_load from the
 # cold scalar cache: GroupNorm family 0.596 -> 0.571 ms per step, +0.6 % end to end on the same box (round 4).
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Wno-pass-failed -mllvm -amdgpu-mfma-vgpr-form -mllvm -amdgpu-kernarg-preload-count=16"
-SRCS="gemm gemm_m0a gemm_m0b gemm_m1 gemm_m2 gemm_m3 gemm_halo gemm_ps gemm_ps2 ffn ffn_wide elementwise attention backward cavp vocoder diag engine"
+# the translation units (NAME.hip), listed once for this script and tools/build_variant*.sh
+SRCS=$(echo $(cat sources.txt))      # one line, single blanks, however the file is wrapped
 mkdir -p build/bf16 build/f16
 pids=()
 for v in bf16 f16; do
   DEF=""; [ $v = f16 ] && DEF="-DDF_OPERAND_F16"
   for f in $SRCS; do
     o=build/$v/$f.o
-    if [ ! -f $o ] || [ $f.hip -nt $o ] || [ common.h -nt $o ] || [ gemm.h -nt $o ] || [ gemm_tiles.def -nt $o ] || [ gemm_impl.h -nt $o ] || [ kernels.h -nt $o ] || [ ../../include/df_engine.h -nt $o ] || [ build.sh -nt $o ]; then
+    if [ ! -f $o ] || [ $f.hip -nt $o ] || [ common.h -nt $o ] || [ gemm.h -nt $o ] || [ gemm_tiles.def -nt $o ] || [ gemm_impl.h -nt $o ] || [ kernels.h -nt $o ] || [ ../../include/df_engine.h -nt $o ] || [ build.sh -nt $o ] ||
+       { [[ $f == engine* ]] && [ engine_internal.h -nt $o ]; }; then
       hipcc $FLAGS $DEF -c $f.hip -o $o &
       pids+=($!)
     fi

@@ -1042,7 +1042,7 @@ hipError_t launch_pack_ffproj(const float* Wp, const float* bp, const float* W2,
 }
 
 namespace {
-// ---- cross-attention with the context folded into per-sample "weights" (engine.hip: context_px).
+// ---- cross-attention with the context folded into per-sample "weights" (engine_builder.hip: context_px).
 // kv [NB*Tc][2C] = (K | V) of the context tokens.  Kexp / Vexp [NB][H*Tcp][C]: row (h, tc) holds the head-h slice of token
 // tc's K (V) in columns [h*D, (h+1)*D) and zeros elsewhere, so that ONE dense GEMM against a C x C weight yields every head's
 // (K_h Wq_h) resp. (Wo_h V_h^T) block.  Rows tc >= Tc are padding (zero).

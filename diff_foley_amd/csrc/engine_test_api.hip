@@ -1,0 +1,518 @@
+// libdfengine: single-kernel entry points for unit tests and tools (df_test_*; include/df_engine.h).
+#include "engine_internal.h"
+
+using namespace dfe;
+
+extern "C" {
+
+// ---- single-kernel entry points for unit tests
+// grow-only split-K scratch shared by the test entry points (no allocation inside timed loops)
+static float* test_partial(size_t bytes) {
+  static float* buf = nullptr;
+  static size_t cap = 0;
+  if (bytes > cap) {
+    if (buf) {
+      (void)hipDeviceSynchronize();
+      (void)hipFree(buf);
+    }
+    HIPCHK(hipMalloc((void**)&buf, bytes));
+    cap = bytes;
+  }
+  return buf;
+}
+
+int df_test_gemm(const uint16_t* A, const uint16_t* W, float* C, int M, int N, int K, int tile, int splitk, void* stream) {
+  return guard([&] {
+    GemmParams g = Builder::gp_linear(A, M, K, W, N);
+    Builder::out_f32(g, C, N);
+    g.dbg = getenv("DF_GEMM_DBG") ? atoi(getenv("DF_GEMM_DBG")) : 0;
+    g.splitk = splitk;
+    if (splitk > 1) g.partial = test_partial((size_t)splitk * M * N * 4);
+    else if (g.dbg & 64) g.partial = test_partial((size_t)4096 * 32 * 8);      // per-block clock stamps (tools/gemm_stamps.py)
+    HIPCHK(launch_gemm(g, tile, 1, (hipStream_t)stream));
+  });
+}
+
+// The GEMM with its simple epilogue features switched on: bias, residual, activation (1 = SiLU, 2 = ReLU), fp32 or
+// operand-type output, with and without split-K -- every tile must give the same answer for every combination.
+int df_test_gemm_epi(const uint16_t* A, const uint16_t* W, const float* bias, const float* res, void* C, int M, int N, int K,
+                     int act, int out_operand, int tile, int splitk, void* stream) {
+  return guard([&] {
+    GemmParams g = Builder::gp_linear(A, M, K, W, N);
+    if (out_operand) Builder::out_b16(g, (bf16_t*)C, N);
+    else Builder::out_f32(g, (float*)C, N);
+    g.bias = bias;
+    if (res) { g.res = res; g.ldr = N; }
+    g.silu = act == 1;
+    g.relu = act == 2;
+    g.splitk = splitk;
+    if (splitk > 1) g.partial = test_partial((size_t)splitk * M * N * 4);
+    if (!gemm_tile_valid(g, tile, 1, splitk)) fail("tile %d / split-K %d refused this problem", tile, splitk);
+    HIPCHK(launch_gemm(g, tile, 1, (hipStream_t)stream));
+  });
+}
+
+// C = [A | A2] W^T with the K columns split over two operand tensors (the merged FF2 + proj_out GEMM of the SpatialTransformer).
+int df_test_gemm_dual(const uint16_t* A, const uint16_t* A2, const uint16_t* W, float* C, int M, int N, int K1, int K2, int tile,
+                      int splitk, void* stream) {
+  return guard([&] {
+    GemmParams g = Builder::gp_linear(A, M, K1, W, N);
+    g.K = K1 + K2;
+    g.w_bytes = Builder::op_bytes((size_t)N * (K1 + K2) * 2);
+    g.A2 = A2; g.lda2 = K2; g.Cin2 = K2; g.a2_bytes = Builder::op_bytes((size_t)M * K2 * 2);
+    Builder::out_f32(g, C, N);
+    g.splitk = splitk;
+    if (splitk > 1) g.partial = test_partial((size_t)splitk * M * N * 4);
+    if (!gemm_tile_valid(g, tile, 1, splitk)) fail("tile %d / split-K %d refused this problem", tile, splitk);
+    HIPCHK(launch_gemm(g, tile, 1, (hipStream_t)stream));
+  });
+}
+
+// Every GemmParams epilogue feature on a caller-chosen (tile, split-K, batch, gm): tests/test_gemm_epilogues_gpu.py walks the
+// autotuner's whole search space with it.
+static void test_gemm_params(const df_test_gemm_desc* d, GemmParams& g) {
+  if (!d) fail("df_test_gemm: null descriptor");
+  if (d->size != (int64_t)sizeof(df_test_gemm_desc))
+    fail("df_test_gemm: descriptor of %lld bytes, this build expects %zu (stale binding of df_test_gemm_desc?)", (long long)d->size,
+         sizeof(df_test_gemm_desc));
+  const bf16_t* A = (const bf16_t*)d->A;
+  const bf16_t* W = (const bf16_t*)d->W;
+  if (d->conv) {
+    if (d->stride != 1 && d->stride != 2) fail("df_test_gemm: conv stride %d", d->stride);
+    g = Builder::gp_conv3(A, d->NB, d->H, d->Wd, d->Cin, W, d->N, d->stride, 0);
+  } else {
+    g = Builder::gp_linear(A, d->M, d->K, W, d->N);
+    if (d->lda > 0) {
+      g.lda = d->lda;
+      g.a_bytes = Builder::op_bytes((size_t)d->M * d->lda * 2);
+    }
+  }
+  g.C = d->C; g.ldc = d->ldc > 0 ? d->ldc : g.N; g.out_bf16 = d->out_operand ? 1 : 0;
+  g.a_bs = d->a_bs; g.w_bs = d->w_bs; g.c_bs = d->c_bs; g.res_bs = d->res_bs;
+  g.alpha = d->alpha;
+  g.bias = d->bias;
+  g.rowbias = d->rowbias; g.ld_rowbias = d->ld_rowbias; g.rows_per_sample = d->rows_per_sample; g.rowbias_mode = d->rowbias_mode;
+  g.res = d->res; g.ldr = d->ldr;
+  g.relu = d->relu; g.silu = d->silu;
+  g.aux = (bf16_t*)d->aux; g.ld_aux = d->ld_aux;
+  g.stats = (float2*)d->stats; g.stats_slots = d->stats_slots;
+  g.ln_stats = (const float2*)d->ln_stats; g.ln_slots = d->ln_slots; g.ln_C = d->ln_C; g.ln_eps = d->ln_eps; g.ln_cs = d->ln_cs;
+  g.w_rows = d->w_rows; g.sm_w = d->sm_w; g.sm_valid = d->sm_valid;
+  g.dup_rows = d->dup_rows; g.no_c_store = d->no_c_store; g.store_nchw = d->store_nchw; g.hw_out = d->hw_out;
+  g.cfg_out = d->cfg_out; g.cfg_scale = d->cfg_scale;
+  g.defer_reduce = d->defer_reduce;
+  g.gm = d->gm;
+  g.splitk = d->splitk > 1 ? d->splitk : 1;
+}
+
+int df_test_gemm_valid(const df_test_gemm_desc* d, int tile, int batch, int splitk) {
+  std::lock_guard<std::recursive_mutex> hold(g_api_lock);
+  try {
+    GemmParams g;
+    test_gemm_params(d, g);
+    return gemm_tile_valid(g, tile, batch, splitk) ? 1 : 0;
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return -1;
+  }
+}
+
+int df_test_gemm_tile_info(int tile, df_test_gemm_tile* out) {
+  std::lock_guard<std::recursive_mutex> hold(g_api_lock);
+  if (tile < 0 || tile >= TILE_ALL || !out || out->size != (int64_t)sizeof(df_test_gemm_tile)) {
+    g_err = "df_test_gemm_tile_info: no tile " + std::to_string(tile) + ", or a df_test_gemm_tile of another size";
+    return 1;
+  }
+  const GemmTileInfo& t = kGemmTiles[tile];
+  out->name = t.name; out->family = t.family; out->modes = t.modes;
+  out->bm = t.bm; out->bn = t.bn; out->dma_threads = gemm_halo_dma_threads(tile); out->ring = t.ring;
+  return 0;
+}
+
+int df_test_gemm_ex(const df_test_gemm_desc* d, void* stream) {
+  return guard([&] {
+    GemmParams g;
+    test_gemm_params(d, g);
+    const int batch = d->batch > 1 ? d->batch : 1;
+    if (g.K % 64 != 0) fail("df_test_gemm: K %d is not a multiple of 64", g.K);
+    if (d->defer_reduce && g.splitk < 2) fail("df_test_gemm: defer_reduce needs split-K");
+    const size_t slab_bytes = (size_t)g.splitk * g.M * g.N * 4;
+    if (g.splitk > 1) g.partial = test_partial(slab_bytes);
+    const hipError_t e = launch_gemm(g, d->tile, batch, (hipStream_t)stream);
+    if (e == hipErrorInvalidValue)
+      fail("launch_gemm refused tile %d / split-K %d / batch %d (%dx%dx%d)", d->tile, g.splitk, batch, g.M, g.N, g.K);
+    HIPCHK(e);
+    if (d->defer_reduce && d->slabs_out)
+      HIPCHK(hipMemcpyAsync(d->slabs_out, g.partial, slab_bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  });
+}
+
+// The folded cross-attention exactly as context_px + the SpatialTransformer plan run it, every intermediate returned:
+// ctx.kv (kv = ctx Wkv^T), xattn_expand (Kexp / Vexp), the lnq_t packing of (norm2.gamma, to_q) (WqT), ctx.g (G = Kexp WqT^T),
+// xattn_rowstats (cs, bb from bq = Wq beta), the batched ctx.vo (Vo[n] = Wo Vexp[n]^T), then st.xs (probabilities P from the
+// operand copy xb of the residual stream x and its per-64-column (sum, sum of squares) statistics) and st.xo (out = x + P Vo^T + bo,
+// fp32).  ctx.kv / ctx.g / ctx.vo run on the 64 x 64 tile; st.xs and st.xo on the caller's tiles.
+int df_test_xattn_chain(const uint16_t* ctx, const uint16_t* Wkv, const float* Wq, const float* gamma, const float* bq,
+                        const uint16_t* Wo, const float* bo, const float* x, const uint16_t* xb, const void* xstats, int NB, int T,
+                        int Tc, int Dc, int C, int heads, uint16_t* kv, uint16_t* Kexp, uint16_t* Vexp, uint16_t* WqT, uint16_t* G,
+                        float* cs, float* bb, uint16_t* Vo, uint16_t* P, float* out, int tile_xs, int tile_xo, void* stream) {
+  return guard([&] {
+    hipStream_t s = (hipStream_t)stream;
+    const int HT = heads * 32, M = NB * T;
+    const float scale = 1.0f / sqrtf((float)(C / heads));
+    if (Tc < 1 || Tc > 32 || C % 64 != 0 || C % heads != 0 || (C / heads) % 8 != 0 || HT % 64 != 0 || T % 64 != 0 || Dc % 64 != 0)
+      fail("xattn chain: C %d / heads %d / Tc %d / T %d / Dc %d outside what the folded form takes", C, heads, Tc, T, Dc);
+    auto run = [&](const GemmParams& g, int tile, int batch, const char* what) {
+      if (!gemm_tile_valid(g, tile, batch, 1)) fail("xattn chain: tile %d refused %s", tile, what);
+      HIPCHK(launch_gemm(g, tile, batch, s));
+    };
+    {
+      GemmParams g = Builder::gp_linear(ctx, NB * Tc, Dc, Wkv, 2 * C);
+      Builder::out_b16(g, kv, 2 * C);
+      run(g, TILE_64x64, 1, "ctx.kv");
+    }
+    HIPCHK(launch_xattn_expand(kv, Kexp, Vexp, NB, Tc, 32, C, heads, s));
+    HIPCHK(launch_pack_lnq_t(Wq, gamma, WqT, C, scale, s));
+    {
+      GemmParams g = Builder::gp_linear(Kexp, NB * HT, C, WqT, C);
+      Builder::out_b16(g, G, C);
+      run(g, TILE_64x64, 1, "ctx.g");
+    }
+    HIPCHK(launch_xattn_rowstats(G, Kexp, bq, scale, C, (long)NB * HT, cs, bb, s));
+    {
+      GemmParams g = Builder::gp_linear(Wo, C, C, Vexp, HT);
+      g.w_bs = (long)HT * C;
+      Builder::out_b16(g, Vo, HT);
+      g.c_bs = (long)C * HT;
+      run(g, TILE_64x64, NB, "ctx.vo");
+    }
+    {
+      GemmParams g = Builder::gp_linear(xb, M, C, G, HT);
+      g.w_bs = (long)HT * C; g.w_rows = T;
+      Builder::out_b16(g, P, HT);
+      g.ln_stats = (const float2*)xstats; g.ln_slots = C / 64; g.ln_C = C; g.ln_eps = 1e-5f; g.ln_cs = cs;
+      g.bias = bb;
+      g.sm_w = 32; g.sm_valid = Tc;
+      run(g, tile_xs, 1, "st.xs");
+    }
+    {
+      GemmParams g = Builder::gp_linear(P, M, HT, Vo, C);
+      g.w_bs = (long)C * HT; g.w_rows = T;
+      Builder::out_f32(g, out, C);
+      g.bias = bo;
+      g.res = x; g.ldr = C;
+      run(g, tile_xo, 1, "st.xo");
+    }
+  });
+}
+
+// FeedForward's second Linear merged with proj_out (launch_pack_ffproj): wout [C][F + C] = [Wp W2 | Wp], bout = Wp b2 + bp.
+int df_test_pack_ffproj(const float* Wp, const float* bp, const float* W2, const float* b2, uint16_t* wout, float* bout, int C, int F,
+                        void* stream) {
+  return guard([&] { HIPCHK(launch_pack_ffproj(Wp, bp, W2, b2, wout, bout, C, F, (hipStream_t)stream)); });
+}
+
+// Producer GEMM (t0 = A0 W0^T + b0 [+ t0_in], fp32 + operand copy + per-row partial statistics) followed by a
+// LayerNorm-folded consumer GEMM (y = LN(t0; gamma, beta) W1^T + b1), exactly the pair the SpatialTransformer plan uses.
+// mode 0: y fp32 [M][N1];  mode 1: GEGLU (W1 = [x ; gate] rows, y operand-type [M][N1/2]);  mode 2: fused QKV --
+// N1 = 3C, y operand-type [M][2C] and vt operand-type [M/T][C][ldvt] (V columns transposed per sample of T rows).
+int df_test_ln_chain(const uint16_t* A0, const uint16_t* W0, const float* b0, const float* res_in, const float* gamma,
+                     const float* beta, const float* W1, const float* b1, float* t0, void* y, uint16_t* vt, int M, int C,
+                     int N1, int mode, int T, int ldvt, int tile0, int sk0, int tile1, int sk1, void* stream) {
+  return guard([&] {
+    hipStream_t s = (hipStream_t)stream;
+    const int slots = C / 64;
+    uint16_t *xb = nullptr, *w1p = nullptr;
+    float2* st = nullptr;
+    float *cs = nullptr, *bb = nullptr;
+    HIPCHK(hipMalloc((void**)&xb, (size_t)M * C * 2));
+    HIPCHK(hipMalloc((void**)&st, (size_t)M * slots * sizeof(float2)));
+    HIPCHK(hipMalloc((void**)&w1p, (size_t)N1 * C * 2));
+    HIPCHK(hipMalloc((void**)&cs, (size_t)N1 * 4));
+    HIPCHK(hipMalloc((void**)&bb, (size_t)N1 * 4));
+    HIPCHK(hipMemsetAsync(st, 0xFF, (size_t)M * slots * sizeof(float2), s));      // NaN poison: every slot must be written
+    HIPCHK(launch_pack_ln_linear(W1, b1, gamma, beta, w1p, cs, bb, N1, C, 0, mode == 1 ? N1 / 2 : 0, s));
+    {
+      GemmParams g = Builder::gp_linear(A0, M, C, W0, C);
+      Builder::out_f32(g, t0, C);
+      g.bias = b0;
+      if (res_in) { g.res = res_in; g.ldr = C; }
+      g.aux = xb; g.ld_aux = C;
+      g.stats = st; g.stats_slots = slots;
+      g.splitk = sk0;
+      if (sk0 > 1) g.partial = test_partial((size_t)sk0 * M * C * 4);
+      if (!gemm_tile_valid(g, tile0, 1, sk0)) fail("producer: tile %d / split-K %d not valid here", tile0, sk0);
+      HIPCHK(launch_gemm(g, tile0, 1, s));
+    }
+    {
+      GemmParams g = Builder::gp_linear(xb, M, C, w1p, N1);
+      g.ln_stats = st; g.ln_slots = slots; g.ln_C = C; g.ln_eps = 1e-5f; g.ln_cs = cs;
+      g.bias = bb;
+      if (mode == 0) Builder::out_f32(g, (float*)y, N1);
+      else if (mode == 1) { Builder::out_b16(g, (bf16_t*)y, N1 / 2); g.geglu = 1; }
+      else {
+        Builder::out_b16(g, (bf16_t*)y, 2 * C);
+        g.vt = vt; g.vt_col0 = 2 * C; g.vt_T = T; g.ldvt = ldvt;
+      }
+      g.splitk = sk1;
+      if (sk1 > 1) g.partial = test_partial((size_t)sk1 * M * N1 * 4);
+      if (!gemm_tile_valid(g, tile1, 1, sk1)) fail("consumer: tile %d / split-K %d not valid here", tile1, sk1);
+      HIPCHK(launch_gemm(g, tile1, 1, s));
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    for (void* p : {(void*)xb, (void*)st, (void*)w1p, (void*)cs, (void*)bb}) (void)hipFree(p);
+  });
+}
+
+// The LayerNorm-folded GEGLU projection alone, on caller-owned operands (timing probes: tools/pgeglu_probe.py).  stats [M][K/64]
+// float2, cs / bias [N1]; dbg = debug switches of the persistent kernel (ffn.hip) or DF_GEMM_DBG of the generic one.
+int df_test_geglu(const uint16_t* A, const uint16_t* W, const void* stats, const float* cs, const float* bias, uint16_t* out, int M,
+                  int K, int N1, int tile, int dbg, void* stream) {
+  return guard([&] {
+    GemmParams g = Builder::gp_linear(A, M, K, W, N1);
+    g.ln_stats = (const float2*)stats; g.ln_slots = K / 64; g.ln_C = K; g.ln_eps = 1e-5f; g.ln_cs = cs;
+    g.bias = bias;
+    Builder::out_b16(g, out, N1 / 2);
+    g.geglu = 1;
+    g.splitk = 1;
+    g.dbg = dbg;
+    if (dbg & 64) g.partial = test_partial((size_t)1024 * 32 * 8);     // per-block clock stamps (read back with df_test_scratch_read)
+    if (gemm_tile_is_wgeglu(tile)) {      // the wide tiles read the 320-column packing: permuted here, per call (test entry)
+      if (N1 % 320 != 0) fail("tile %d: N = %d is not a multiple of 320", tile, N1);
+      static void* buf = nullptr;
+      static size_t cap = 0;
+      const size_t need = (size_t)N1 * K * 2 + (size_t)N1 * 8 + 512;
+      if (need > cap) {
+        if (buf) HIPCHK(hipFree(buf));
+        HIPCHK(hipMalloc(&buf, need));
+        cap = need;
+      }
+      uint16_t* w3 = (uint16_t*)buf;
+      float* cs3 = (float*)((char*)buf + (((size_t)N1 * K * 2 + 255) & ~(size_t)255));
+      float* bb3 = cs3 + N1;
+      static const void* packed_from = nullptr;
+      if (!(dbg & 128) || packed_from != (const void*)W)      // dbg bit 7 (timing tools): keep the packing made from this W by the last call
+        HIPCHK(launch_pack_w320(W, cs, bias, w3, cs3, bb3, N1, K, (hipStream_t)stream));
+      packed_from = (const void*)W;
+      g.dbg = dbg & ~128;
+      g.W_w320 = w3; g.cs_w320 = cs3; g.bias_w320 = bb3;
+    }
+    if (!gemm_tile_valid(g, tile, 1, 1)) fail("tile %d not valid for this GEGLU projection", tile);
+    HIPCHK(launch_gemm(g, tile, 1, (hipStream_t)stream));
+  });
+}
+
+int df_test_scratch_read(void* host, int64_t bytes) {
+  return guard([&] {
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(host, test_partial((size_t)bytes), (size_t)bytes, hipMemcpyDeviceToHost));
+  });
+}
+
+int df_test_linear_rows(const float* a, int lda, const uint16_t* W, const float* bias, float* out, int ldo, int M, int N, int K,
+                        int act, void* stream) {
+  return guard([&] { HIPCHK(launch_linear_rows(a, lda, W, bias, out, ldo, M, N, K, act, (hipStream_t)stream)); });
+}
+
+// ONE block of the loaded UNet in isolation, against the reference's per-block tensors (golden G3): the plan builder's
+// own resblock / spatial_transformer / Downsample / Upsample code paths on caller-supplied NHWC fp32 activations.
+//   kind 0 ResBlock (semb = SiLU(time_embed(t)) [N][4*model_channels]), 1 SpatialTransformer (context [N][T][context_dim]),
+//   2 Downsample, 3 Upsample.  x [N*H*W][Cin] -> out [N*OH*OW][Cout], both NHWC fp32.
+int df_test_unet_block(df_ctx* c, const char* prefix, int kind, const float* x, const float* semb, const float* context,
+                       float* out, int N, int H, int W, int Cin, int Cout, int T, void* stream) {
+  return guard([&] {
+    if (!c->has_unet || !c->finalized) fail("df_test_unet_block: load and finalize a UNet first");
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    const df_unet_config& u = c->ucfg;
+    const std::string pre = "model.diffusion_model.", p = prefix;
+    Plan plan;
+    Builder b{c, &plan, pre, 0};
+    const int rows = N * H * W, temb = 4 * u.model_channels;
+    F32 xin{b.buf<float>((size_t)rows * Cin), rows, Cin, Cin};
+    HIPCHK(hipMemcpyAsync(xin.p, x, (size_t)rows * Cin * 4, hipMemcpyDeviceToDevice, s));
+    int orow = rows;
+    if (kind == 2) orow = rows / 4;
+    if (kind == 3) orow = rows * 4;
+    F32 dst{b.buf<float>((size_t)orow * Cout), orow, Cout, Cout};
+    if (kind == 0) {
+      float* E = b.buf<float>((size_t)N * Cout);
+      const bf16_t* w = c->w_linear(pre + p + ".emb_layers.1.weight");
+      const float* bb = c->f32(pre + p + ".emb_layers.1.bias");
+      b.other("t.embproj", [=](hipStream_t st, const RunArgs&) { return launch_linear_rows(semb, temb, w, bb, E, Cout, N, Cout, temb, 0, st); });
+      b.resblock(xin, dst, N, H, W, p + ".in_layers.0", p + ".in_layers.2", p + ".out_layers.0", p + ".out_layers.3",
+                 p + ".skip_connection", 1e-5f, E, Cout, 0);
+    } else if (kind == 1) {
+      const int Dc = u.context_dim, ldvtc = rup(T, 32);
+      bf16_t* ctxb = b.buf<bf16_t>((size_t)N * T * Dc);
+      const long n = (long)N * T * Dc;
+      b.other("ctx.cast", [=](hipStream_t st, const RunArgs&) { return launch_cast_bf16(context, ctxb, n, st); });
+      if (Builder::px_ok(Cin, u.num_heads, T, H * W)) {     // same choice as build_unet_like
+        Builder::PX px = b.context_px(ctxb, N, T, Dc, p, Cin, u.num_heads);
+        b.spatial_transformer(xin, dst, N, H * W, p, u.num_heads, nullptr, nullptr, T, ldvtc, &px);
+      } else {
+        bf16_t *K, *Vt;
+        b.context_kv(ctxb, N, T, Dc, p, Cin, &K, &Vt, ldvtc);
+        b.spatial_transformer(xin, dst, N, H * W, p, u.num_heads, K, Vt, T, ldvtc);
+      }
+    } else {
+      bf16_t* hb = b.cast2d(xin);
+      const std::string wn = pre + p + (kind == 2 ? ".op" : ".conv");
+      GemmParams g = kind == 3 ? Builder::gp_conv3_ups4(hb, N, H, W, Cin, c->w_conv3_ups4(wn + ".weight", Cin), Cout)   // as in the plan
+                               : Builder::gp_conv3(hb, N, H, W, Cin, c->w_conv3(wn + ".weight", Cin), Cout, kind == 2 ? 2 : 1, 0);
+      Builder::out_f32(g, dst.p, Cout);
+      g.bias = c->f32(wn + ".bias");
+      b.gemm(g, 1, kind == 2 ? "down" : "up");
+    }
+    finish_plan(c, &plan);
+    RunArgs a;
+    run_ops(c, &plan, 0, plan.ops.size(), s, a);
+    HIPCHK(hipMemcpyAsync(out, dst.p, (size_t)orow * Cout * 4, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));
+  });
+}
+
+int df_test_conv3x3(const uint16_t* A, const uint16_t* W, const float* bias, float* C, int NB, int H, int Wd, int Cin,
+                    int Cout, int stride, int ups, int tile, int splitk, void* stream) {
+  return guard([&] {
+    GemmParams g = Builder::gp_conv3(A, NB, H, Wd, Cin, W, Cout, stride, ups);
+    Builder::out_f32(g, C, Cout);
+    g.bias = bias;
+    g.splitk = splitk;
+    g.dbg = getenv("DF_GEMM_DBG") ? atoi(getenv("DF_GEMM_DBG")) : 0;
+    if (splitk > 1) g.partial = test_partial((size_t)splitk * g.M * g.N * 4);
+    else if (g.dbg & 64) g.partial = test_partial((size_t)4096 * 32 * 8);      // halo kernels: per-block clock stamps
+    HIPCHK(launch_gemm(g, tile, 1, (hipStream_t)stream));
+  });
+}
+
+int df_test_conv3x3_fewout(const uint16_t* A, const uint16_t* W, const float* bias, float* out_nchw, int NB, int H, int Wd, int Cin,
+                           int Cout, void* stream) {
+  return guard([&] { HIPCHK(launch_conv3x3_fewout(A, W, bias, out_nchw, NB, H, Wd, Cin, Cout, (hipStream_t)stream)); });
+}
+
+int df_test_conv3x3_skip(const uint16_t* A, const uint16_t* A2, const uint16_t* W, const float* bias, float* C, int NB, int H,
+                         int Wd, int Cin, int Cin2, int Cout, int tile, int splitk, void* stream) {
+  return guard([&] {
+    GemmParams g = Builder::gp_conv3(A, NB, H, Wd, Cin, W, Cout, 1, 0);
+    Builder::out_f32(g, C, Cout);
+    g.bias = bias;
+    g.A2 = A2; g.lda2 = Cin2; g.Cin2 = Cin2; g.a2_bytes = Builder::op_bytes((size_t)g.M * Cin2 * 2);
+    g.K = 9 * Cin + Cin2;
+    g.w_bytes = Builder::op_bytes((size_t)Cout * g.K * 2);
+    g.splitk = splitk;
+    if (splitk > 1) g.partial = test_partial((size_t)splitk * g.M * g.N * 4);
+    if (!gemm_tile_valid(g, tile, 1, splitk)) fail("tile %d / split-K %d refused this problem", tile, splitk);
+    HIPCHK(launch_gemm(g, tile, 1, (hipStream_t)stream));
+  });
+}
+
+// Upsample + conv3x3 through the phase-decomposed form (gemm_m3.hip): W_oihw fp32 [Cout][Cin][3][3] is packed here.
+int df_test_conv3x3_ups4(const uint16_t* A, const float* W_oihw, const float* bias, float* C, uint16_t* w4_scratch, int NB, int H,
+                         int Wd, int Cin, int Cout, int tile, int splitk, void* stream) {
+  return guard([&] {
+    HIPCHK(launch_pack_conv_ups4(W_oihw, w4_scratch, Cout, Cin, Cin, (hipStream_t)stream));
+    GemmParams g = Builder::gp_conv3_ups4(A, NB, H, Wd, Cin, w4_scratch, Cout);
+    Builder::out_f32(g, C, Cout);
+    g.bias = bias;
+    g.splitk = splitk;
+    if (splitk > 1) g.partial = test_partial((size_t)splitk * 4 * g.M * g.N * 4);
+    if (!gemm_tile_valid(g, tile, 1, splitk)) fail("tile %d / split-K %d refused this problem", tile, splitk);
+    HIPCHK(launch_gemm(g, tile, 1, (hipStream_t)stream));
+  });
+}
+
+int df_test_groupnorm(const float* x, int ld, int N, int HW, int C, const float* gamma, const float* beta, float eps,
+                      int silu, uint16_t* out, void* stream) {
+  return guard([&] {
+    const size_t sb = groupnorm_scratch_bytes(N, HW, C);
+    if (sb) {
+      float* scr = test_partial(sb);
+      HIPCHK(launch_groupnorm_chunked(x, ld, N, HW, C, gamma, beta, eps, silu, out, C, nullptr, scr, (hipStream_t)stream));
+    } else {
+      HIPCHK(launch_groupnorm(x, ld, N, HW, C, gamma, beta, eps, silu, out, C, nullptr, (hipStream_t)stream));
+    }
+  });
+}
+int df_test_groupnorm_own_slabs(float* x, int ld, int N, int HW, int C, const float* gamma, const float* beta, float eps, int silu,
+                                uint16_t* out, const float* slabs, int nslab, int c_own, const float* bias, const float* res,
+                                int ldr, void* stream) {
+  return guard([&] {
+    if (!groupnorm_accepts_slabs(HW, C)) fail("groupnorm: %d x %d slab does not fit the register kernel", HW, C);
+    HIPCHK(launch_groupnorm_own_slabs(x, ld, N, HW, C, gamma, beta, eps, silu, out, C, nullptr, slabs, nslab,
+                                      (long)N * HW * c_own, c_own, bias, res, ldr, (hipStream_t)stream));
+  });
+}
+int df_test_layernorm(const float* x, int rows, int C, const float* gamma, const float* beta, uint16_t* out, void* stream) {
+  return guard([&] { HIPCHK(launch_layernorm(x, C, rows, C, gamma, beta, 1e-5f, out, (hipStream_t)stream)); });
+}
+int df_test_attention(const uint16_t* Q, int ldq, const uint16_t* K, int ldk, const uint16_t* Vt, int ldvt, uint16_t* O,
+                      int ldo, int N, int heads, int D, int Tq, int Tk, float scale, void* stream) {
+  return guard([&] { HIPCHK(launch_attention(Q, ldq, K, ldk, Vt, ldvt, O, ldo, N, heads, D, Tq, Tk, scale, (hipStream_t)stream)); });
+}
+
+// ---- the classifier's input-gradient kernels (csrc/backward.hip) one at a time
+int df_test_groupnorm_bwd(const float* x, int ld, int N, int HW, int C, const float* gamma, const float* beta, float eps, int silu,
+                          const float* dy, int lddy, const float* addend, int ldadd, float* dx, int lddx, uint16_t* dx_b16,
+                          void* stream) {
+  return guard([&] {
+    HIPCHK(launch_groupnorm_bwd(x, ld, N, HW, C, gamma, beta, eps, silu, dy, lddy, addend, ldadd, dx, lddx, dx_b16,
+                                (hipStream_t)stream));
+  });
+}
+int df_test_layernorm_bwd(const float* x, int rows, int C, const float* gamma, float eps, const float* dy, const float* addend,
+                          float* dx, uint16_t* dx_b16, void* stream) {
+  return guard([&] { HIPCHK(launch_layernorm_bwd(x, rows, C, gamma, eps, dy, addend, dx, dx_b16, (hipStream_t)stream)); });
+}
+int df_test_geglu_fwd(const uint16_t* u, uint16_t* y, int64_t rows, int H, void* stream) {
+  return guard([&] { HIPCHK(launch_geglu_fwd(u, y, (long)rows, H, (hipStream_t)stream)); });
+}
+int df_test_geglu_bwd(const uint16_t* u, const float* dy, uint16_t* du, int64_t rows, int H, void* stream) {
+  return guard([&] { HIPCHK(launch_geglu_bwd(u, dy, du, (long)rows, H, (hipStream_t)stream)); });
+}
+int df_test_attention_bwd(const uint16_t* Q, int ldq, const uint16_t* K, int ldk, const uint16_t* Vt, int ldvt, const float* dO,
+                          int lddo, uint16_t* dQ, int lddq, uint16_t* dK, int lddk, uint16_t* dV, int lddv, int N, int heads, int D,
+                          int Tq, int Tk, float scale, int form, void* stream) {
+  return guard([&] {
+    size_t nws = attention_bwd_ws_floats(N, heads, D, Tq, Tk, lddk, lddv, dK != nullptr);
+    if (form == 2 && dK) nws = (size_t)N * heads * Tq * 3;      // the tiled pair forced on a shape a resident form would take
+    float* ws = nws ? test_partial(nws * 4) : nullptr;
+    HIPCHK(launch_attention_bwd(Q, ldq, K, ldk, Vt, ldvt, dO, lddo, dQ, lddq, dK, lddk, dV, lddv, N, heads, D, Tq, Tk, scale, ws,
+                                form, (hipStream_t)stream));
+  });
+}
+int df_test_cls_head_bwd(const float* prob, const float* w, float* dh, uint16_t* dh_b16, int N, int HW, int C, int Cp, void* stream) {
+  return guard([&] { HIPCHK(launch_cls_head_bwd(prob, w, dh, dh_b16, N, HW, C, Cp, (hipStream_t)stream)); });
+}
+int df_test_pack_linear_t(const float* w, uint16_t* out, int O, int I, int ldo, int off, void* stream) {
+  return guard([&] { HIPCHK(launch_pack_linear_t(w, out, O, I, ldo, off, (hipStream_t)stream)); });
+}
+int df_test_pack_conv_bwd(const float* w, uint16_t* out, int O, int I, int Opad, void* stream) {
+  return guard([&] { HIPCHK(launch_pack_conv_bwd(w, out, O, I, Opad, (hipStream_t)stream)); });
+}
+// Backward-data of a 3x3 conv (pad 1) exactly as build_classifier_grad issues it: W_oihw fp32 [O][I][3][3] packed here with
+// Opad = O rounded up to 64 (dY: [NB][OH][OW][Opad], pad columns zero); stride 1 = conv of dY with the flipped taps, stride 2 = the
+// same over the zero-stuffed x2 grid of dY (Downsample^T).  dX fp32 [NB][H][W][I] (+ the operand-type copy dX_op when given).
+int df_test_conv3x3_bwd_data(const uint16_t* dY, const float* W_oihw, uint16_t* w_scratch, float* dX, uint16_t* dX_op, int NB, int H,
+                             int Wd, int I, int O, int stride, int tile, int splitk, void* stream) {
+  return guard([&] {
+    if (stride != 1 && stride != 2) fail("conv3x3 backward-data: stride %d", stride);
+    if (stride == 2 && ((H | Wd) & 1)) fail("conv3x3 backward-data: stride 2 needs an even map, got %dx%d", H, Wd);
+    const int Opad = (O + 63) / 64 * 64;
+    HIPCHK(launch_pack_conv_bwd(W_oihw, w_scratch, O, I, Opad, (hipStream_t)stream));
+    GemmParams g = stride == 1 ? Builder::gp_conv3(dY, NB, H, Wd, Opad, w_scratch, I, 1, 0)
+                               : Builder::gp_conv3(dY, NB, H / 2, Wd / 2, Opad, w_scratch, I, 1, 1);
+    if (stride == 2) g.zstuff = 1;
+    Builder::out_f32(g, dX, I);
+    if (dX_op) {
+      g.aux = dX_op;
+      g.ld_aux = I;
+    }
+    g.splitk = splitk;
+    if (splitk > 1) g.partial = test_partial((size_t)splitk * g.M * g.N * 4);
+    if (!gemm_tile_valid(g, tile, 1, splitk)) fail("tile %d / split-K %d refused this problem", tile, splitk);
+    HIPCHK(launch_gemm(g, tile, 1, (hipStream_t)stream));
+  });
+}
+
+}  // extern "C"

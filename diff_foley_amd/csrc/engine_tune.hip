@@ -1,0 +1,286 @@
+// libdfengine: the autotuner -- tune key, the process-wide tune cache, and the three-stage autotune_plan (types: engine_internal.h).
+#include "engine_internal.h"
+
+DFE_NAMESPACE {
+
+// Autotune, stage 1: time every (tile, split-K) candidate of every distinct GEMM of the plan in isolation (3 launches
+// back to back, operands cache-warm) and rank them ("measure, don't guess").
+// Stage 2 (in situ): the isolated ranking mispredicts layers whose operands arrive cold from HBM/MALL or whose
+// neighbours leave the CUs half busy, so the best DF_TUNE_TOPK candidates of every GEMM are re-timed INSIDE the plan:
+// round r runs the whole plan with every GEMM on its r-th candidate (HIP events around each op), and each distinct
+// GEMM keeps the candidate with the smallest in-plan time summed over its instances.
+namespace {
+struct TuneCand { int tile, sk; float iso_ms; double situ_ms; };
+
+static std::string tune_key(const Op& o) {
+  const GemmParams& g = o.gp;
+  char key[160];
+  const int epi = (g.silu ? 128 : 0) | (g.ln_stats ? 1 : 0) | (g.stats ? 2 : 0) | (g.vt ? 4 : 0) | (g.aux ? 8 : 0) | (g.res ? 16 : 0) | (g.Cin2 ? 32 : 0) |
+                  (o.defer ? 64 : 0) | (g.dup_rows ? 256 : 0);
+  snprintf(key, sizeof key, "%d_%d_%d_%d_%d_%d_%d_%d_e%d", g.M, g.N, g.K, g.taps, g.stride, g.ups, o.batch, g.geglu, epi);
+  return key;
+}
+}  // namespace
+
+std::map<std::string, TuneChoice>& tune_cache() {
+  static std::map<std::string, TuneChoice> m;
+  static bool loaded = false;
+  if (!loaded) {
+    loaded = true;
+    if (const char* path = getenv("DF_TUNE_CACHE")) {
+      if (FILE* f = fopen(path, "r")) {
+        char key[160];
+        TuneChoice ch;
+        while (fscanf(f, "%159s %d %d %d", key, &ch.tile, &ch.sk, &ch.gm) == 4) m[key] = ch;
+        fclose(f);
+      }
+    }
+  }
+  return m;
+}
+static void tune_cache_save() {
+  const char* path = getenv("DF_TUNE_CACHE");
+  if (!path) return;
+  FILE* f = fopen(path, "w");
+  if (!f) return;
+  for (auto& kv : tune_cache()) fprintf(f, "%s %d %d %d\n", kv.first.c_str(), kv.second.tile, kv.second.sk, kv.second.gm);
+  fclose(f);
+}
+
+// Set by df_tune_cache_import: another rank's choices were handed to this process.  Plans then take every choice the cache holds
+// for their GEMMs whether or not df_autotune is on here -- the ranks of a job must run the SAME tiles and split-K factors
+// (identical fp32 summation order, bit-equal results; parallel.broadcast_packed_model), and an importing rank that never asked
+// for tuning used to fall back to the heuristic tiles silently.
+bool g_tune_imported = false;
+
+// A GEMM the table does not hold takes the entry of its NEAREST ROW COUNT among the entries that agree in everything else
+// (N, K, taps, stride, upsampling, batch count, GEGLU, epilogue class): the table is made at sampler batches 1-8 and 16, and another
+// batch size or latent width changes M only -- the tile family that wins at M = 8192 still wins at 10240.  Within a factor of 4 in M;
+// the choice is validated for the actual problem like an exact hit.  (Round 6: B = 10 without this ran the cost-model plan.)
+static const TuneChoice* nearest_tune_choice(const std::string& key) {
+  const size_t us = key.find('_');
+  if (us == std::string::npos) return nullptr;
+  const std::string suffix = key.substr(us);
+  const double m = (double)atol(key.substr(0, us).c_str());
+  if (m <= 0) return nullptr;
+  const TuneChoice* best = nullptr;
+  double bestd = 2.0001;           // |log2(M' / M)| <= 2
+  for (auto& kv : tune_cache()) {
+    const size_t u2 = kv.first.find('_');
+    if (u2 == std::string::npos || kv.first.compare(u2, std::string::npos, suffix) != 0) continue;
+    const double m2 = (double)atol(kv.first.substr(0, u2).c_str());
+    if (m2 <= 0) continue;
+    const double d = fabs(log2(m2 / m));
+    if (d < bestd) {
+      bestd = d;
+      best = &kv.second;
+    }
+  }
+  return best;
+}
+
+void apply_tune_cache(Plan* pl) {
+  auto& tc = tune_cache();
+  for (auto& o : pl->ops) {
+    if (!o.is_gemm || o.c_ext) continue;
+    const std::string key = tune_key(o);
+    auto it = tc.find(key);
+    const TuneChoice* chp = it != tc.end() ? &it->second : nearest_tune_choice(key);
+    if (!chp) continue;
+    const TuneChoice& ch = *chp;
+    const size_t need = (size_t)ch.sk * o.gp.M * o.gp.N * 4 * (o.gp.taps == 4 ? 4 : 1);
+    if (!gemm_tile_valid(o.gp, ch.tile, o.batch, ch.sk) || (ch.sk > 1 && need > pl->partial_bytes)) continue;
+    o.tile = ch.tile;
+    o.gp.splitk = ch.sk;
+    o.gp.gm = ch.gm;
+    o.gp.partial = pl->partial;
+  }
+}
+
+void autotune_plan(df_ctx* c, Plan* pl, hipStream_t s) {
+  {
+    auto& tc = tune_cache();      // in-memory for the life of the process (+ the file when DF_TUNE_CACHE is set)
+    bool all = !tc.empty();
+    for (auto& o : pl->ops)
+      if (o.is_gemm && !o.c_ext && !tc.count(tune_key(o))) all = false;
+    if (all) {
+      apply_tune_cache(pl);
+      tune_cache_save();     // DF_TUNE_CACHE may name a file this process has not written yet
+      return;
+    }
+  }
+  struct SaveOnExit {
+    Plan* pl;
+    ~SaveOnExit() {
+      for (auto& o : pl->ops)
+        if (o.is_gemm && !o.c_ext) tune_cache()[tune_key(o)] = {o.tile, o.gp.splitk, o.gp.gm};
+      tune_cache_save();
+    }
+  } save_on_exit{pl};
+  hipEvent_t e0, e1;
+  HIPCHK(hipEventCreate(&e0));
+  HIPCHK(hipEventCreate(&e1));
+  std::map<std::string, std::vector<TuneCand>> cands;
+  static const int tile_cap = getenv("DF_TILE_CAP") ? atoi(getenv("DF_TILE_CAP")) : TILE_ALL;   // tools: A/B a tile family
+  // Candidates per GEMM class that go on to the in-plan stage.  The isolated ranking is a weak predictor of the in-plan time
+  // (operands cold, neighbours' traffic): widening 6 -> 12 -> 40 measured 231.2 -> 235.8 and 232.5 -> 233.7 -> 234.5 steps/s on
+  // two boxes, for ~1 s more tuning per plan (40 plan runs of 4 ms x 4 repetitions).
+  static const int topk = getenv("DF_TUNE_TOPK") ? atoi(getenv("DF_TUNE_TOPK")) : 32;           // 1 = stage 1 only
+  for (auto& o : pl->ops) {
+    if (!o.is_gemm || o.c_ext) continue;
+    const std::string key = tune_key(o);
+    if (cands.count(key)) continue;
+    GemmParams g = o.gp;
+    std::vector<TuneCand>& v = cands[key];
+    static const unsigned long tile_skip = getenv("DF_TILE_SKIP") ? strtoul(getenv("DF_TILE_SKIP"), nullptr, 0) : 0ul;   // tools: bit mask
+    for (int t = 0; t < TILE_ALL && t < tile_cap; ++t) {
+      if ((tile_skip >> t) & 1) continue;
+      // 3 * 2^k splits too: 2 M tiles x 20 N tiles x 6 = 240 blocks fill 256 CUs where 4 / 8 give 160 / 320 (tools/cold_probe.py:
+      // sk 3 / 6 / 12 are the best factor of most weight-streaming layers)
+      static const int sks[] = {1, 2, 3, 4, 6, 8, 12, 16, 24, 32};
+      for (int si = 0; si < 10; ++si) {
+        const int sk = sks[si];
+        if (!gemm_tile_valid(g, t, o.batch, sk)) { if (sk > 1) break; else continue; }
+        const size_t need = (size_t)sk * g.M * g.N * 4 * (g.taps == 4 ? 4 : 1);
+        if (sk > 1 && need > pl->partial_bytes) break;
+        GemmParams q = g;
+        q.splitk = sk;
+        q.partial = pl->partial;
+        // res may alias C: results are garbage during tuning but are recomputed by the next real run
+        if (launch_gemm(q, t, o.batch, s) != hipSuccess) continue;
+        HIPCHK(hipEventRecord(e0, s));
+        for (int r = 0; r < 3; ++r) (void)launch_gemm(q, t, o.batch, s);
+        HIPCHK(hipEventRecord(e1, s));
+        HIPCHK(hipEventSynchronize(e1));
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+        v.push_back({t, sk, ms, 0.0});
+      }
+    }
+    if (v.empty()) v.push_back({o.tile, g.splitk, 0.f, 0.0});
+    std::sort(v.begin(), v.end(), [](const TuneCand& a, const TuneCand& b) { return a.iso_ms < b.iso_ms; });
+    if ((int)v.size() > topk) v.resize(topk > 0 ? topk : 1);
+  }
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  auto apply = [&](int round) {   // round < 0: the best in-situ candidate
+    for (auto& o : pl->ops) {
+      if (!o.is_gemm || o.c_ext) continue;
+      const std::vector<TuneCand>& v = cands[tune_key(o)];
+      int idx = 0;
+      if (round >= 0) idx = std::min(round, (int)v.size() - 1);
+      else
+        for (int k = 1; k < (int)v.size(); ++k)
+          if (v[k].situ_ms < v[idx].situ_ms) idx = k;
+      o.tile = v[idx].tile;
+      o.gp.splitk = v[idx].sk;
+      o.gp.partial = pl->partial;
+    }
+  };
+  size_t rounds = 0;
+  for (auto& kv : cands) rounds = std::max(rounds, kv.second.size());
+  if (rounds <= 1) { apply(0); return; }
+  // stage 2: dummy external buffers (timing does not depend on the values)
+  const size_t slab = std::max((size_t)32 << 20, (pl->ext_hint + 4095) & ~(size_t)4095);
+  char* ext = nullptr;
+  HIPCHK(hipMalloc((void**)&ext, 5 * slab));
+  HIPCHK(hipMemsetAsync(ext, 0, 5 * slab, s));
+  RunArgs a;
+  a.x = (const float*)ext;
+  a.t = (const float*)(ext + slab);
+  a.aux = (const float*)(ext + 2 * slab);
+  a.out = (float*)(ext + 3 * slab);
+  a.out2 = (float*)(ext + 4 * slab);
+  const bool prof_was = c->prof_on;
+  // per-op minimum over `nrep` in-plan runs of the whole plan (a first run warms up)
+  auto time_ops = [&](int nrep) {
+    std::vector<float> best(pl->ops.size(), 1e30f);
+    for (int rep = 0; rep < nrep + 1; ++rep) {
+      c->prof_on = true;
+      c->prof_used = 0;
+      c->prof_fam.clear();
+      c->prof_op.clear();
+      run_ops(c, pl, 0, pl->ops.size(), s, a);
+      c->prof_on = false;
+      HIPCHK(hipStreamSynchronize(s));
+      if (rep == 0) continue;
+      for (size_t i = 0; i < pl->ops.size(); ++i) {
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, c->prof_ev[2 * i], c->prof_ev[2 * i + 1]));
+        best[i] = std::min(best[i], ms);
+      }
+    }
+    return best;
+  };
+  // one in-plan pass over candidate ranks [0, nr): every GEMM class runs its r-th candidate, per-op minimum over `nrep` runs
+  auto evaluate = [&](size_t nr, int nrep) {
+    for (auto& kv : cands)
+      for (auto& cd : kv.second) cd.situ_ms = 0.0;
+    for (size_t r = 0; r < nr; ++r) {
+      apply((int)r);
+      const std::vector<float> best = time_ops(nrep);
+      for (size_t i = 0; i < pl->ops.size(); ++i) {
+        const Op& o = pl->ops[i];
+        if (!o.is_gemm || o.c_ext) continue;
+        std::vector<TuneCand>& v = cands[tune_key(o)];
+        // a deferred split-K reduce is paid by the next op (the GroupNorm sums the slabs): judge the pair.  (round 5) Any consumer
+        // that is not a GEMM itself (GroupNorm, attention: their time depends on nothing in this round but where this GEMM's tile
+        // walk left their input -- which XCD's L2 holds it) is judged with its producer too.
+        const bool pair = i + 1 < pl->ops.size() && (o.defer || !pl->ops[i + 1].is_gemm);
+        if (r < v.size()) v[r].situ_ms += best[i] + (pair ? best[i + 1] : 0.f);
+      }
+    }
+  };
+  // stage 2a: every surviving candidate, coarse (2 runs); 2b: the four best of each class again, among good neighbours and
+  // with 6 runs -- the final choice between near-equal candidates used to flip from run to run (227 .. 234 steps/s for the
+  // same build and box), a second, finer round takes most of that variance out
+  evaluate(rounds, 2);
+  size_t keep = 0;
+  for (auto& kv : cands) {
+    std::vector<TuneCand>& v = kv.second;
+    std::sort(v.begin(), v.end(), [](const TuneCand& x, const TuneCand& y) { return x.situ_ms < y.situ_ms; });
+    if (v.size() > 4) v.resize(4);
+    keep = std::max(keep, v.size());
+  }
+  evaluate(keep, 6);
+  apply(-1);
+  if (getenv("DF_TUNE_LOG") && atoi(getenv("DF_TUNE_LOG"))) {      // tools: the candidates of every GEMM class, both stages
+    for (auto& kv : cands) {
+      fprintf(stderr, "[df tune] %s:", kv.first.c_str());
+      for (auto& cd : kv.second) fprintf(stderr, "  t%d/sk%d iso %.1f situ %.1f", cd.tile, cd.sk, cd.iso_ms * 1e3 / 3, cd.situ_ms * 1e3);
+      fprintf(stderr, "\n");
+    }
+  }
+  // stage 3: tile walk order of the chosen tile (GemmParams::gm), again timed inside the plan
+  static const int gms[] = {0, 1, 2, 4, 8, 16};
+  constexpr int NG = sizeof(gms) / sizeof(gms[0]);
+  std::map<std::string, std::vector<double>> score;
+  for (int r = 0; r < NG; ++r) {
+    for (auto& o : pl->ops)
+      if (o.is_gemm && !o.c_ext) o.gp.gm = gms[r];
+    const std::vector<float> best = time_ops(3);
+    for (size_t i = 0; i < pl->ops.size(); ++i) {
+      const Op& o = pl->ops[i];
+      if (!o.is_gemm || o.c_ext) continue;
+      std::vector<double>& v = score[tune_key(o)];
+      v.resize(NG, 0.0);
+      v[r] += best[i] + ((i + 1 < pl->ops.size() && !pl->ops[i + 1].is_gemm) ? best[i + 1] : 0.f);
+    }
+  }
+  for (auto& o : pl->ops) {
+    if (!o.is_gemm || o.c_ext) continue;
+    const std::vector<double>& v = score[tune_key(o)];
+    int bi = 0;
+    for (int k = 1; k < NG; ++k)
+      if (v[k] < v[bi] * 0.99) bi = k;      // keep the default walk unless another is >1 % faster
+    o.gp.gm = gms[bi];
+  }
+  c->prof_on = prof_was;
+  c->prof_used = 0;
+  c->prof_fam.clear();
+  c->prof_op.clear();
+  HIPCHK(hipStreamSynchronize(s));
+  (void)hipFree(ext);
+}
+
+}  // namespace dfe

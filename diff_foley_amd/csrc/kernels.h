@@ -85,7 +85,7 @@ hipError_t launch_pack_ln_linear(const float* w, const float* bias, const float*
                                  hipStream_t s);
 // conv3x3 OIHW + 1x1 skip weight [O][I2] -> operand rows [O][9*I + I2] (taps (ky,kx,ci), then the skip channels)
 hipError_t launch_pack_conv_skip(const float* w, const float* ws, uint16_t* out, int O, int I, int I2, hipStream_t s);
-// ---- cross-attention with the context folded into per-sample weights (see engine.hip context_px)
+// ---- cross-attention with the context folded into per-sample weights (see engine_builder.hip context_px)
 hipError_t launch_xattn_expand(const uint16_t* kv, uint16_t* Kexp, uint16_t* Vexp, int NB, int Tc, int Tcp, int C, int H,
                                hipStream_t s);
 hipError_t launch_pack_lnq_t(const float* Wq, const float* gamma, uint16_t* out, int C, float scale, hipStream_t s);

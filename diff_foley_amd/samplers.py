@@ -50,7 +50,7 @@ def reject_unsupported(sampler, kwargs, extra=None):
 
 
 def _is_table_error(ex):
-    """The engine's two messages for a missing / outgrown hoisted timestep table (csrc/engine.hip unet_forward_ts)."""
+    """The engine's two messages for a missing / outgrown hoisted timestep table (unet_run in the C ABI unit of csrc)."""
     msg = str(ex)
     return "no timestep table" in msg or "outside the table" in msg or "hoistable" in msg
 

@@ -368,7 +368,7 @@ typedef struct df_test_gemm_tile {
   int family, bm, bn, dma_threads, ring, modes;
 } df_test_gemm_tile;
 int df_test_gemm_tile_info(int tile, df_test_gemm_tile* out);
-/* The folded cross-attention of one SpatialTransformer (engine.hip context_px, st.xs, st.xo), every intermediate out: ctx [NB*Tc][Dc]
+/* The folded cross-attention of one SpatialTransformer (engine_builder.hip context_px, st.xs, st.xo), every intermediate out: ctx [NB*Tc][Dc]
  * and Wkv [2C][Dc] (to_k | to_v) operand type; Wq [C][C], gamma (norm2), bq = Wq . beta fp32; Wo [C][C] operand, bo fp32; x fp32
  * [NB*T][C], xb its operand copy, xstats float2 [NB*T][C/64] (sum, sum of squares per 64 columns).  Outputs: kv [NB*Tc][2C],
  * Kexp / Vexp [NB][H*32][C], WqT [C][C], G [NB][H*32][C], cs / bb [NB][H*32], Vo [NB][C][H*32], P [NB*T][H*32], out fp32 [NB*T][C]. */

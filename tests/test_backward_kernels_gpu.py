@@ -1,5 +1,5 @@
 """GPU: each kernel of the classifier's hand-written input-gradient pass (csrc/backward.hip, the backward-data GEMM modes of
-engine.hip:build_classifier_grad) on its own, through the df_test_* entry points, against torch autograd in FLOAT64 on the CPU of the
+engine_cls_grad.hip:build_classifier_grad) on its own, through the df_test_* entry points, against torch autograd in FLOAT64 on the CPU of the
 same op.  Operand inputs are rounded to the build's operand type first (bf16 / fp16, both builds via the `prec` fixture), so the
 reference sees exactly the values the kernel reads.
 

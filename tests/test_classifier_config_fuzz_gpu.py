@@ -1,4 +1,4 @@
-"""Randomised differential test of the hand-written classifier backward pass (csrc/backward.hip, engine.hip:build_classifier_grad)
+"""Randomised differential test of the hand-written classifier backward pass (csrc/backward.hip, engine_cls_grad.hip:build_classifier_grad)
 over classifier CONFIGURATIONS: seeded draws of the Classifier_Backbone's constructor arguments (alignment_backbone.py:420-640:
 model_channels, channel_mult, num_res_blocks, attention_resolutions, num_heads, context_dim), procedurally generated weights, and
 ``d sum(log p) / d x`` (cal_classifier_loglikelihood_grad, ddim.py:333-341) from ``df_classifier_grad`` against torch autograd through

@@ -1,6 +1,6 @@
 """GPU: every GEMM epilogue the plan uses, on every (tile, split-K) pair the autotuner may pick for it.
 
-autotune_plan (csrc/engine.hip) times each GEMM on tiles 0 .. TILE_ALL-1 with split-K 1, 2, 3, 4, 6, 8, 12, 16, 24, 32, where the
+autotune_plan (csrc/engine_tune.hip) times each GEMM on tiles 0 .. TILE_ALL-1 with split-K 1, 2, 3, 4, 6, 8, 12, 16, 24, 32, where the
 first split-K > 1 that gemm_tile_valid refuses ends that tile's walk; whichever pair is fastest becomes production code on that
 machine.  Each case below is one plan epilogue (csrc/gemm.h GemmParams) at a small shape chosen so that its edges occur, run
 through df_test_gemm_ex on exactly that set of pairs.

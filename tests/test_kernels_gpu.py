@@ -87,7 +87,7 @@ def test_gemm(tile, M, N, K, splitk):
 @pytest.mark.parametrize("M,N,K1,K2,splitk", [(200, 320, 1280, 320, 1), (72, 192, 512, 128, 2), (512, 1280, 5120, 1280, 4),
                                               (64, 64, 64, 64, 1)])
 def test_gemm_two_operand_tensors(tile, M, N, K1, K2, splitk):
-    """K columns [0, K1) from A, [K1, K1+K2) from A2: the merged FF2 + proj_out GEMM (engine.hip st.ffproj)."""
+    """K columns [0, K1) from A, [K1, K1+K2) from A2: the merged FF2 + proj_out GEMM (engine_builder.hip st.ffproj)."""
     E = _eng()
     a = bf(rnd((M, K1), 21)).cuda()
     a2 = bf(rnd((M, K2), 22)).cuda()

@@ -720,7 +720,7 @@ def test_apply_model_context_cache_is_not_fooled_by_address_reuse(full):
 
 @pytest.mark.parametrize("Tc", [32, 17, 1])
 def test_full_cross_attention_forms_agree(full, monkeypatch, Tc):
-    """Cross-attention against operands precomputed from the context (engine.hip context_px: score GEMM with softmax
+    """Cross-attention against operands precomputed from the context (engine_builder.hip context_px: score GEMM with softmax
     epilogue + output GEMM) vs the q-projection -> attention kernel -> out-projection form (DF_NO_XPRE=1), also for context
     lengths below the 32-column head group (masked softmax).  attention_openai.py:152-194."""
     x, c = rnd((2, 4, 16, 64), 300 + Tc), rnd((2, Tc, 768), 301 + Tc)
@@ -740,7 +740,7 @@ def test_full_cross_attention_forms_agree(full, monkeypatch, Tc):
 
 
 def test_tiny_autotuned_plans_match_untuned(P):
-    """The on-device autotuner (isolated ranking + in-situ refinement, engine.hip autotune_plan) only changes tile /
+    """The on-device autotuner (isolated ranking + in-situ refinement, engine_tune.hip autotune_plan) only changes tile /
     split-K choices: an autotuned engine must reproduce the golden vectors for every plan type."""
     from diff_foley_amd import synth
     m = P.LatentDiffusion(**P.stage2_config(synth.UNET_TINY, synth.VAE_TINY, synth.COND_TINY))
@@ -1068,7 +1068,7 @@ def test_facade_runs_the_shipped_plan_table(P, tmp_path):
 
 def test_batch_outside_the_shipped_table_takes_its_nearest_entries(full, tmp_path):
     """A sampler batch the shipped table does not hold (B = 10: UNet batch 20) builds its plan from the entries of the nearest row
-    count (engine.hip nearest_tune_choice: another batch size changes M only), not from the cost model -- the plan carries the
+    count (engine_tune.hip nearest_tune_choice: another batch size changes M only), not from the cost model -- the plan carries the
     producer-specialised / wide tiles -- and, samples being independent, its row 0 equals the B = 1 run to operand-rounding noise."""
     import csv
     import os

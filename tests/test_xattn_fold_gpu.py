@@ -1,4 +1,4 @@
-"""GPU: the folded cross-attention (engine.hip context_px, st.xs, st.xo) kernel by kernel and as one chain, on both builds.
+"""GPU: the folded cross-attention (engine_builder.hip context_px, st.xs, st.xo) kernel by kernel and as one chain, on both builds.
 
 df_test_xattn_chain runs the plan's sequence -- ctx.kv, xattn_expand, the lnq_t packing, ctx.g, xattn_rowstats, the batched ctx.vo,
 st.xs, st.xo -- and returns every intermediate.  Each is compared with its defining formula (csrc/elementwise.hip xattn_expand /

@@ -5,7 +5,7 @@ set -e
 name=$1; shift
 cd "$(dirname "$0")/../diff_foley_amd/csrc"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Wno-pass-failed -mllvm -amdgpu-mfma-vgpr-form -mllvm -amdgpu-kernarg-preload-count=16 -DDF_OPERAND_F16 $*"
-SRCS="gemm gemm_m0a gemm_m0b gemm_m1 gemm_m2 gemm_m3 gemm_halo gemm_ps gemm_ps2 ffn elementwise attention backward cavp vocoder diag engine"
+SRCS=$(echo $(cat sources.txt))      # one line, single blanks, however the file is wrapped
 d=build/var_$name; mkdir -p $d ab
 pids=()
 for f in $SRCS; do hipcc $FLAGS -c $f.hip -o $d/$f.o & pids+=($!); done
