@@ -305,26 +305,20 @@ template <int D>
 hipError_t launch_d(const uint16_t* Q, int ldq, const uint16_t* K, int ldk, const uint16_t* Vt, int ldvt,
                     uint16_t* O, int ldo, int N, int heads, int Tq, int Tk, float scale, hipStream_t s) {
   const float sl2 = scale * 1.4426950408889634f;
-  if constexpr (D <= 80) {        // two 64-key buffers of K and V^T fit beside each other (<= 35 KB)
-    if (Tq >= 128 && Tk % 64 == 0) {
-      dim3 grid((Tq + 127) / 128, heads, N);
-      hipLaunchKernelGGL((attention_kernel<D, 4, 2>), grid, dim3(256), 0, s, Q, ldq, K, ldk, Vt, ldvt, heads, Tq, Tk, sl2, O, ldo);
-      return hipGetLastError();
-    }
+  const int form = attention_form(D, Tq, Tk), nw = form >> 4;
+  if (nw < 1) return hipErrorInvalidValue;
+  const dim3 grid((Tq + 32 * nw - 1) / (32 * nw), heads, N), block(64 * nw);
+#define DF_ATTN(...) hipLaunchKernelGGL((attention_kernel<D, __VA_ARGS__>), grid, block, 0, s, Q, ldq, K, ldk, Vt, ldvt, heads, Tq, Tk, sl2, O, ldo)
+  switch (form) {
+    case 4 * 16 + 2:
+      if constexpr (D <= 80) { DF_ATTN(4, 2); break; }      // two 64-key buffers of K and V^T fit beside each other (<= 35 KB)
+      return hipErrorInvalidValue;
+    case 4 * 16 + 1: DF_ATTN(4); break;
+    case 2 * 16 + 1: DF_ATTN(2); break;
+    case 1 * 16 + 1: DF_ATTN(1); break;
+    default: return hipErrorInvalidValue;
   }
-  if (Tq >= 128) {
-    dim3 grid((Tq + 127) / 128, heads, N);
-    hipLaunchKernelGGL((attention_kernel<D, 4>), grid, dim3(256), 0, s, Q, ldq, K, ldk, Vt, ldvt, heads, Tq, Tk, sl2,
-                       O, ldo);
-  } else if (Tq >= 64) {
-    dim3 grid((Tq + 63) / 64, heads, N);
-    hipLaunchKernelGGL((attention_kernel<D, 2>), grid, dim3(128), 0, s, Q, ldq, K, ldk, Vt, ldvt, heads, Tq, Tk, sl2,
-                       O, ldo);
-  } else {
-    dim3 grid((Tq + 31) / 32, heads, N);
-    hipLaunchKernelGGL((attention_kernel<D, 1>), grid, dim3(64), 0, s, Q, ldq, K, ldk, Vt, ldvt, heads, Tq, Tk, sl2,
-                       O, ldo);
-  }
+#undef DF_ATTN
   return hipGetLastError();
 }
 
@@ -339,6 +333,12 @@ bool attention_supported(int D) {
       return true;
     default: return false;
   }
+}
+
+int attention_form(int D, int Tq, int Tk) {
+  if (!attention_supported(D)) return 0;
+  if (Tq >= 128) return 4 * 16 + (D <= 80 && Tk % 64 == 0 ? 2 : 1);
+  return (Tq >= 64 ? 2 : 1) * 16 + 1;
 }
 
 hipError_t launch_attention(const uint16_t* Q, int ldq, const uint16_t* K, int ldk, const uint16_t* Vt, int ldvt,

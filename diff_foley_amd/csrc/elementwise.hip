@@ -475,10 +475,12 @@ __global__ void pack_latent_kernel(const float* __restrict__ x, bf16_t* __restri
   const float* xp = x + (long)b * C * HW + px;        // any C <= cpad (the reference's in_channels / z_channels are constructor arguments)
   bf16_t* o = out + i * cpad;
   if (wpq) {
+    // accumulated in double: where the C terms cancel, fp32 round-off of terms ~10 is several fp16 ulps of a result ~1e-4
+    // (one launch of B * HW threads per decode: the cost is nothing)
     for (int oc = 0; oc < C; ++oc) {
-      float s = bpq[oc];
-      for (int c = 0; c < C; ++c) s += wpq[oc * C + c] * (xp[(long)c * HW] * in_scale);
-      o[oc] = f2bf(s);
+      double s = bpq[oc];
+      for (int c = 0; c < C; ++c) s += (double)wpq[oc * C + c] * ((double)xp[(long)c * HW] * (double)in_scale);
+      o[oc] = f2bf((float)s);
     }
   } else {
     for (int c = 0; c < C; ++c) o[c] = f2bf(xp[(long)c * HW] * in_scale);
@@ -675,12 +677,6 @@ inline int grid_for(long n, int block = 256, int cap = 4096) {
 
 }  // namespace
 
-bool groupnorm_accepts_slabs(int HW, int C) {      // shapes the register kernel takes (launch_groupnorm_sl)
-  if (C % 64 != 0 || (long)HW * (C / 64) > 16384) return false;
-  const int half = C / 64, rmax = std::min(HW, 1024 / half);
-  return rmax > 0 && (HW + rmax - 1) / rmax <= 20;
-}
-
 size_t groupnorm_scratch_bytes(int N, int HW, int C) {
   const long items = (long)HW * (C / 64);
   if (items <= 16384 || (C != 128 && C != 256 && C != 512)) return 0;      // register kernels / generic streaming kernel
@@ -727,38 +723,49 @@ hipError_t launch_groupnorm_own_slabs(float* x, int ld, int N, int HW, int C, co
   return launch_groupnorm_sl(x, ld, N, HW, C, gamma, beta, eps, silu, out, ldo, raw_out, sl, s);
 }
 
+// The form launch_groupnorm_sl runs: PER of groupnorm_reg_kernel (thread layout: R rows per pass x (cpg / 2) channel pairs, PER
+// passes), GN_FORM_STREAMING, or GN_FORM_REFUSED (the streaming kernel has no slab path).
+static int groupnorm_sl_form(int HW, int C, int nslab) {
+  if (C <= 0 || C % 64 != 0) return GN_FORM_REFUSED;
+  const int half = C / 64;
+  const long items = (long)HW * half;
+  const int rmax = std::min(HW, 1024 / half);
+  const int need = rmax > 0 ? (HW + rmax - 1) / rmax : 1 << 30;
+  if (items > 16384 || need > 20) return nslab > 0 ? GN_FORM_REFUSED : GN_FORM_STREAMING;
+  for (int per : {1, 2, 3, 4, 6, 8, 12, 16})
+    if (need <= per) return per;
+  return 20;
+}
+
+bool groupnorm_accepts_slabs(int HW, int C) { return groupnorm_sl_form(HW, C, 1) != GN_FORM_REFUSED; }      // the register kernel's shapes
+
+int groupnorm_form(int N, int HW, int C, int nslab) {
+  if (nslab == 0 && groupnorm_scratch_bytes(N, HW, C)) return GN_FORM_CHUNKED;
+  return groupnorm_sl_form(HW, C, nslab);
+}
+
 static hipError_t launch_groupnorm_sl(const float* x, int ld, int N, int HW, int C, const float* gamma, const float* beta,
                                       float eps, int silu, uint16_t* out, int ldo, uint16_t* raw_out, const GnSlabs& sl,
                                       hipStream_t s) {
-  if (C % 64 != 0) return hipErrorInvalidValue;
-  const int cpg = C / 32;
-  const long items = (long)HW * (cpg / 2);
-  const int nslab = sl.n;
-  if (nslab > 0 && items > 16384) return hipErrorInvalidValue;     // the streaming kernel has no slab path
-  // thread layout of groupnorm_reg_kernel: R rows per pass x (cpg / 2) channel pairs, PER passes
-  const int half = cpg / 2;
-  const int rmax = std::min(HW, 1024 / std::max(half, 1));
-  const int need = rmax > 0 ? (HW + rmax - 1) / rmax : 1 << 30;
+  const int form = groupnorm_sl_form(HW, C, sl.n);
+  if (form == GN_FORM_REFUSED) return hipErrorInvalidValue;
+  const int cpg = C / 32, half = cpg / 2;
 #define DF_GN_REG(PER)                                                                                                \
-  {                                                                                                                   \
+  case PER: {                                                                                                         \
     const int R = (HW + (PER) - 1) / (PER);                                                                           \
     const int threads = (half * R + 63) & ~63;                                                                        \
     hipLaunchKernelGGL(groupnorm_reg_kernel<PER>, dim3(32 * N), dim3(threads), 0, s, x, ld, HW, cpg, R, sl.n, N, sl.own, \
                        sl.c_own, sl.stride, out, ldo, silu, C, gamma, beta, eps, raw_out, sl);                        \
+    break;                                                                                                            \
   }
-  if (items > 16384 || need > 20 || half < 1) {
-    if (nslab > 0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(groupnorm_kernel, dim3(32, N), dim3(1024), 0, s, x, ld, HW, C, cpg, gamma, beta, eps, silu, out,
-                       ldo, raw_out);
-  } else if (need <= 1) DF_GN_REG(1)
-  else if (need <= 2) DF_GN_REG(2)
-  else if (need <= 3) DF_GN_REG(3)
-  else if (need <= 4) DF_GN_REG(4)
-  else if (need <= 6) DF_GN_REG(6)
-  else if (need <= 8) DF_GN_REG(8)
-  else if (need <= 12) DF_GN_REG(12)
-  else if (need <= 16) DF_GN_REG(16)
-  else DF_GN_REG(20)
+  switch (form) {
+    case GN_FORM_STREAMING:
+      hipLaunchKernelGGL(groupnorm_kernel, dim3(32, N), dim3(1024), 0, s, x, ld, HW, C, cpg, gamma, beta, eps, silu, out,
+                         ldo, raw_out);
+      break;
+    DF_GN_REG(1) DF_GN_REG(2) DF_GN_REG(3) DF_GN_REG(4) DF_GN_REG(6) DF_GN_REG(8) DF_GN_REG(12) DF_GN_REG(16) DF_GN_REG(20)
+    default: return hipErrorInvalidValue;
+  }
 #undef DF_GN_REG
   return hipGetLastError();
 }

@@ -422,29 +422,50 @@ int df_test_conv3x3_ups4(const uint16_t* A, const float* W_oihw, const float* bi
   });
 }
 
-int df_test_groupnorm(const float* x, int ld, int N, int HW, int C, const float* gamma, const float* beta, float eps,
-                      int silu, uint16_t* out, void* stream) {
+// Which kernel form a shape takes (host only; csrc/kernels.h groupnorm_form / attention_form -- the functions the launchers
+// themselves dispatch on): tests/test_kernel_forms_cpu.py asserts that the GPU tests' shape tables reach every form.
+int df_test_groupnorm_form(int N, int HW, int C, int nslab) { return groupnorm_form(N, HW, C, nslab); }
+int df_test_attention_form(int D, int Tq, int Tk) { return attention_form(D, Tq, Tk); }
+
+// GroupNorm in its three input modes with every leading dimension free: plain (nslab == 0; the chunked form where
+// groupnorm_form says so), a split-K producer's slabs (nslab > 0: x is the first slab, + bias + rowbias) and the norm's own
+// producer (own_slabs != null: df_test_groupnorm_own_slabs with ldo / raw_out).  raw_out rows are ldo wide like out's.
+int df_test_groupnorm_ex(float* x, int ld, int N, int HW, int C, const float* gamma, const float* beta, float eps, int silu,
+                         uint16_t* out, int ldo, uint16_t* raw_out, int nslab, int64_t slab_stride, const float* bias,
+                         const float* rowbias, int ld_rowbias, const float* own_slabs, int c_own, const float* res, int ldr,
+                         void* stream) {
   return guard([&] {
-    const size_t sb = groupnorm_scratch_bytes(N, HW, C);
-    if (sb) {
-      float* scr = test_partial(sb);
-      HIPCHK(launch_groupnorm_chunked(x, ld, N, HW, C, gamma, beta, eps, silu, out, C, nullptr, scr, (hipStream_t)stream));
+    hipStream_t s = (hipStream_t)stream;
+    const int form = groupnorm_form(N, HW, C, nslab);
+    if (form == GN_FORM_REFUSED) fail("groupnorm: %d x %d with %d slabs is refused", HW, C, nslab);
+    if (own_slabs) {
+      HIPCHK(launch_groupnorm_own_slabs(x, ld, N, HW, C, gamma, beta, eps, silu, out, ldo, raw_out, own_slabs, nslab, (long)slab_stride,
+                                        c_own, bias, res, ldr, s));
+    } else if (form == GN_FORM_CHUNKED) {
+      float* scr = test_partial(groupnorm_scratch_bytes(N, HW, C));
+      HIPCHK(launch_groupnorm_chunked(x, ld, N, HW, C, gamma, beta, eps, silu, out, ldo, raw_out, scr, s));
     } else {
-      HIPCHK(launch_groupnorm(x, ld, N, HW, C, gamma, beta, eps, silu, out, C, nullptr, (hipStream_t)stream));
+      HIPCHK(launch_groupnorm_slabs(x, ld, N, HW, C, gamma, beta, eps, silu, out, ldo, raw_out, nslab, (long)slab_stride, bias, rowbias,
+                                    ld_rowbias, s));
     }
   });
+}
+int df_test_groupnorm(const float* x, int ld, int N, int HW, int C, const float* gamma, const float* beta, float eps,
+                      int silu, uint16_t* out, void* stream) {
+  return df_test_groupnorm_ex(const_cast<float*>(x), ld, N, HW, C, gamma, beta, eps, silu, out, C, nullptr, 0, 0, nullptr, nullptr, 0,
+                              nullptr, 0, nullptr, 0, stream);
 }
 int df_test_groupnorm_own_slabs(float* x, int ld, int N, int HW, int C, const float* gamma, const float* beta, float eps, int silu,
                                 uint16_t* out, const float* slabs, int nslab, int c_own, const float* bias, const float* res,
                                 int ldr, void* stream) {
-  return guard([&] {
-    if (!groupnorm_accepts_slabs(HW, C)) fail("groupnorm: %d x %d slab does not fit the register kernel", HW, C);
-    HIPCHK(launch_groupnorm_own_slabs(x, ld, N, HW, C, gamma, beta, eps, silu, out, C, nullptr, slabs, nslab,
-                                      (long)N * HW * c_own, c_own, bias, res, ldr, (hipStream_t)stream));
-  });
+  return df_test_groupnorm_ex(x, ld, N, HW, C, gamma, beta, eps, silu, out, C, nullptr, nslab, (int64_t)N * HW * c_own, bias, nullptr, 0,
+                              slabs, c_own, res, ldr, stream);
+}
+int df_test_layernorm_ex(const float* x, int ld, int rows, int C, const float* gamma, const float* beta, uint16_t* out, void* stream) {
+  return guard([&] { HIPCHK(launch_layernorm(x, ld, rows, C, gamma, beta, 1e-5f, out, (hipStream_t)stream)); });
 }
 int df_test_layernorm(const float* x, int rows, int C, const float* gamma, const float* beta, uint16_t* out, void* stream) {
-  return guard([&] { HIPCHK(launch_layernorm(x, C, rows, C, gamma, beta, 1e-5f, out, (hipStream_t)stream)); });
+  return df_test_layernorm_ex(x, C, rows, C, gamma, beta, out, stream);
 }
 int df_test_attention(const uint16_t* Q, int ldq, const uint16_t* K, int ldk, const uint16_t* Vt, int ldvt, uint16_t* O,
                       int ldo, int N, int heads, int D, int Tq, int Tk, float scale, void* stream) {
@@ -514,5 +535,77 @@ int df_test_conv3x3_bwd_data(const uint16_t* dY, const float* W_oihw, uint16_t* 
     HIPCHK(launch_gemm(g, tile, 1, (hipStream_t)stream));
   });
 }
+
+
+// ---- the packing, casting, pooling and data-movement kernels one at a time (tests/test_small_kernels_gpu.py)
+#define DF_TEST_LAUNCH(call) return guard([&] { HIPCHK(call); })
+int df_test_softmax_rows(const float* s, uint16_t* p, int rows, int T, int ldp, void* stream) {
+  DF_TEST_LAUNCH(launch_softmax_rows(s, p, rows, T, ldp, (hipStream_t)stream));
+}
+int df_test_timestep_embedding(const float* t, float* out, int N, int dim, void* stream) {
+  DF_TEST_LAUNCH(launch_timestep_embedding(t, out, N, dim, (hipStream_t)stream));
+}
+int df_test_timestep_embedding_b16(const float* t, int t_B, uint16_t* out, int N, int dim, void* stream) {
+  DF_TEST_LAUNCH(launch_timestep_embedding_b16(t, t_B, out, N, dim, (hipStream_t)stream));
+}
+int df_test_pack_latent(const float* x, uint16_t* out, int B, int C, int HW, int cpad, int rep, float in_scale, const float* wpq,
+                        const float* bpq, void* stream) {
+  DF_TEST_LAUNCH(launch_pack_latent(x, out, B, C, HW, cpad, rep, in_scale, wpq, bpq, (hipStream_t)stream));
+}
+int df_test_pack_latent_bcast(const float* x, uint16_t* out, int B, int C, int HW, int cpad, int rep, const float* src, float* dst,
+                              int rows, int n, void* stream) {
+  DF_TEST_LAUNCH(launch_pack_latent_bcast(x, out, B, C, HW, cpad, rep, src, dst, rows, n, (hipStream_t)stream));
+}
+int df_test_bcast_rows(const float* src, float* dst, int rows, int n, void* stream) {
+  DF_TEST_LAUNCH(launch_bcast_rows(src, dst, rows, n, (hipStream_t)stream));
+}
+int df_test_cast_bf16(const float* x, uint16_t* out, int64_t n, void* stream) {
+  DF_TEST_LAUNCH(launch_cast_bf16(x, out, (long)n, (hipStream_t)stream));
+}
+int df_test_cast_bf16_2d(const float* x, int ld, uint16_t* out, int64_t rows, int C, void* stream) {
+  DF_TEST_LAUNCH(launch_cast_bf16_2d(x, ld, out, (long)rows, C, (hipStream_t)stream));
+}
+int df_test_avgpool(const float* x, float* out, int N, int HW, int C, void* stream) {
+  DF_TEST_LAUNCH(launch_avgpool(x, out, N, HW, C, (hipStream_t)stream));
+}
+int df_test_pack_conv_weight(const float* w, uint16_t* out, int O, int I, int KH, int KW, int Ipad, void* stream) {
+  DF_TEST_LAUNCH(launch_pack_conv_weight(w, out, O, I, KH, KW, Ipad, (hipStream_t)stream));
+}
+int df_test_pack_conv_skip(const float* w, const float* ws, uint16_t* out, int O, int I, int I2, void* stream) {
+  DF_TEST_LAUNCH(launch_pack_conv_skip(w, ws, out, O, I, I2, (hipStream_t)stream));
+}
+int df_test_pack_geglu(const float* w, const float* b, uint16_t* wout, float* bout, int half_rows, int K, void* stream) {
+  DF_TEST_LAUNCH(launch_pack_geglu(w, b, wout, bout, half_rows, K, (hipStream_t)stream));
+}
+int df_test_pack_ln_linear(const float* w, const float* bias, const float* gamma, const float* beta, uint16_t* wout, float* cs, float* bb,
+                           int rows, int K, int row_off, int geglu_half, void* stream) {
+  DF_TEST_LAUNCH(launch_pack_ln_linear(w, bias, gamma, beta, wout, cs, bb, rows, K, row_off, geglu_half, (hipStream_t)stream));
+}
+int df_test_grad_scale_per_sample(float* x, const float* prob, int N, int64_t per, void* stream) {
+  DF_TEST_LAUNCH(launch_grad_scale_per_sample(x, prob, N, (long)per, (hipStream_t)stream));
+}
+int df_test_stem_im2col(const float* x, uint16_t* out, int F, int H, int W, int OH, int OW, int KP, void* stream) {
+  DF_TEST_LAUNCH(launch_stem_im2col(x, out, F, H, W, OH, OW, KP, (hipStream_t)stream));
+}
+int df_test_maxpool3x3s2(const uint16_t* x, uint16_t* out, int F, int H, int W, int OH, int OW, int C, void* stream) {
+  DF_TEST_LAUNCH(launch_maxpool3x3s2(x, out, F, H, W, OH, OW, C, (hipStream_t)stream));
+}
+int df_test_subsample2(const uint16_t* x, uint16_t* out, int F, int H, int W, int C, void* stream) {
+  DF_TEST_LAUNCH(launch_subsample2(x, out, F, H, W, C, (hipStream_t)stream));
+}
+int df_test_tcat3(const uint16_t* x, uint16_t* out, int F, int T, int HW, int C, void* stream) {
+  DF_TEST_LAUNCH(launch_tcat3(x, out, F, T, HW, C, (hipStream_t)stream));
+}
+int df_test_pack_conv3d_bn(const float* w, const float* gamma, const float* beta, const float* mean, const float* var, float eps,
+                           uint16_t* out, float* bias, int O, int I, int KT, int KH, int KW, int KP, void* stream) {
+  DF_TEST_LAUNCH(launch_pack_conv3d_bn(w, gamma, beta, mean, var, eps, out, bias, O, I, KT, KH, KW, KP, (hipStream_t)stream));
+}
+int df_test_maxpool_time(const float* x, float* out, int B, int T, int C, int k, void* stream) {
+  DF_TEST_LAUNCH(launch_maxpool_time(x, out, B, T, C, k, (hipStream_t)stream));
+}
+int df_test_l2norm_rows(float* x, int rows, int C, void* stream) {
+  DF_TEST_LAUNCH(launch_l2norm_rows(x, rows, C, (hipStream_t)stream));
+}
+#undef DF_TEST_LAUNCH
 
 }  // extern "C"

@@ -14,6 +14,11 @@ hipError_t launch_groupnorm_slabs(const float* x, int ld, int N, int HW, int C, 
                                   float eps, int silu, uint16_t* out, int ldo, uint16_t* raw_out, int nslab,
                                   long slab_stride, const float* bias, const float* rowbias, int ld_rowbias, hipStream_t s);
 bool groupnorm_accepts_slabs(int HW, int C);
+// The form a GroupNorm of this shape runs: PER of the register kernel (1, 2, 3, 4, 6, 8, 12, 16 or 20), or one of the codes below.
+// nslab > 0: a split-K producer's slabs are summed on the fly (either slab path); nslab == 0 includes the callers' switch to
+// launch_groupnorm_chunked when groupnorm_scratch_bytes() is non-zero.  launch_groupnorm* dispatch on this function.
+enum { GN_FORM_STREAMING = -1, GN_FORM_CHUNKED = -2, GN_FORM_REFUSED = -3 };
+int groupnorm_form(int N, int HW, int C, int nslab);
 // x is the NOT-YET-REDUCED output of its own split-K producer: channels [0, c_own) are summed from nslab slabs (leading
 // dimension c_own), bias and the fp32 residual `res` are added in the reduce kernel's order and the result is written back
 // to x before it is normalised; channels [c_own, C) are read from x (the skip half of a concat buffer).
@@ -41,6 +46,8 @@ hipError_t launch_attention(const uint16_t* Q, int ldq, const uint16_t* K, int l
                             uint16_t* O, int ldo, int N, int heads, int D, int Tq, int Tk, float scale,
                             hipStream_t s);
 bool attention_supported(int D);
+// The kernel launch_attention runs: (wavefronts per block) * 16 + (32-key sub-tiles per loop iteration); 0 = refused.
+int attention_form(int D, int Tq, int Tk);
 
 // 3x3 convolution with <= 4 output channels, NHWC operand-type input -> NCHW fp32 output (elementwise.hip; the VAE decoder's conv_out)
 bool conv3x3_fewout_ok(int H, int W, int C, int Cout);

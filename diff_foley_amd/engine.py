@@ -165,7 +165,13 @@ _SIGS = {
                           C.c_void_p, C.c_void_p],
     "df_test_groupnorm_own_slabs": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_int,
                                     C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],
+    "df_test_groupnorm_form": [C.c_int] * 4,
+    "df_test_attention_form": [C.c_int] * 3,
+    "df_test_groupnorm_ex": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p,
+                             C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                             C.c_int, C.c_void_p],
     "df_test_layernorm": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "df_test_layernorm_ex": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "df_test_attention": [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
                           C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p],
     "df_test_groupnorm_bwd": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_int,
@@ -184,6 +190,27 @@ _SIGS = {
     "df_test_gemm_tile_info": [C.c_int, C.POINTER(GemmTile)],
     "df_test_xattn_chain": [C.c_void_p] * 10 + [C.c_int] * 6 + [C.c_void_p] * 10 + [C.c_int, C.c_int, C.c_void_p],
     "df_test_pack_ffproj": [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p],
+    "df_test_softmax_rows": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p],
+    "df_test_timestep_embedding": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p],
+    "df_test_timestep_embedding_b16": [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p],
+    "df_test_pack_latent": [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_float, C.c_void_p, C.c_void_p, C.c_void_p],
+    "df_test_pack_latent_bcast": [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p],
+    "df_test_bcast_rows": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p],
+    "df_test_cast_bf16": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p],
+    "df_test_cast_bf16_2d": [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p],
+    "df_test_avgpool": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p],
+    "df_test_pack_conv_weight": [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p],
+    "df_test_pack_conv_skip": [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p],
+    "df_test_pack_geglu": [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p],
+    "df_test_pack_ln_linear": [C.c_void_p] * 7 + [C.c_int] * 4 + [C.c_void_p],
+    "df_test_grad_scale_per_sample": [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p],
+    "df_test_stem_im2col": [C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p],
+    "df_test_maxpool3x3s2": [C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p],
+    "df_test_subsample2": [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p],
+    "df_test_tcat3": [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p],
+    "df_test_pack_conv3d_bn": [C.c_void_p] * 5 + [C.c_float, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p],
+    "df_test_maxpool_time": [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p],
+    "df_test_l2norm_rows": [C.c_void_p, C.c_int, C.c_int, C.c_void_p],
     "df_test_peak": [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p],
     "df_test_fill": [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_void_p],
 }

@@ -302,8 +302,25 @@ int df_test_groupnorm(const float* x_dev, int ld, int N, int HW, int C, const fl
 int df_test_groupnorm_own_slabs(float* x_dev, int ld, int N, int HW, int C, const float* gamma, const float* beta, float eps,
                                 int silu, uint16_t* out_dev, const float* slabs_dev, int nslab, int c_own,
                                 const float* bias_dev, const float* res_dev, int ldr, void* stream);
+/* Host only, no GPU work: the kernel form a shape takes, from the function the launcher itself dispatches on.
+ * df_test_groupnorm_form: PER of the register kernel (1, 2, 3, 4, 6, 8, 12, 16, 20), -1 streaming kernel, -2 chunked three-launch
+ * form, -3 refused; nslab > 0 = either slab mode.  df_test_attention_form: waves * 16 + 32-key sub-tiles per iteration (66 =
+ * <D,4,2>, 65 = <D,4>, 33 = <D,2>, 17 = <D,1>), 0 = head dim not supported. */
+int df_test_groupnorm_form(int N, int HW, int C, int nslab);
+int df_test_attention_form(int D, int Tq, int Tk);
+/* GroupNorm with every leading dimension free, in its three input modes.  out / raw_out (nullable: the input cast to the operand
+ * type) are [N*HW][ldo].  nslab == 0: plain input x [N*HW][ld].  nslab > 0, own_slabs NULL: x is the first of nslab fp32 slabs
+ * [N*HW][ld], slab_stride floats apart, + bias[C] + rowbias[N][ld_rowbias] (nullable).  own_slabs non-NULL: as
+ * df_test_groupnorm_own_slabs (slabs [N*HW][c_own], slab_stride apart; res [N*HW][ldr]). */
+int df_test_groupnorm_ex(float* x_dev, int ld, int N, int HW, int C, const float* gamma, const float* beta, float eps, int silu,
+                         uint16_t* out_dev, int ldo, uint16_t* raw_out_dev, int nslab, int64_t slab_stride, const float* bias_dev,
+                         const float* rowbias_dev, int ld_rowbias, const float* own_slabs_dev, int c_own, const float* res_dev,
+                         int ldr, void* stream);
+/* x fp32 [rows][C] -> operand type [rows][C], C = 64 .. 2048 in steps of 64; _ex: x rows are ld >= C floats apart */
 int df_test_layernorm(const float* x_dev, int rows, int C, const float* gamma, const float* beta, uint16_t* out_dev,
                       void* stream);
+int df_test_layernorm_ex(const float* x_dev, int ld, int rows, int C, const float* gamma, const float* beta, uint16_t* out_dev,
+                         void* stream);
 int df_test_attention(const uint16_t* Q, int ldq, const uint16_t* K, int ldk, const uint16_t* Vt, int ldvt, uint16_t* O,
                       int ldo, int N, int heads, int D, int Tq, int Tk, float scale, void* stream);
 /* The classifier's input-gradient kernels one at a time (csrc/backward.hip).  Nullable: addend, dx_b16 (its rows are C wide). */
@@ -329,6 +346,33 @@ int df_test_pack_conv_bwd(const float* w_dev, uint16_t* out_dev, int O, int I, i
 int df_test_conv3x3_bwd_data(const uint16_t* dY_dev, const float* W_oihw_dev, uint16_t* w_scratch_dev, float* dX_dev,
                              uint16_t* dX_op_dev, int NB, int H, int Wd, int I, int O, int stride, int tile, int splitk,
                              void* stream);
+/* The packing, casting, pooling and data-movement kernels one at a time: each entry is its launcher (csrc/kernels.h documents
+ * the layouts).  2-byte buffers hold the build's operand type. */
+int df_test_softmax_rows(const float* s_dev, uint16_t* p_dev, int rows, int T, int ldp, void* stream);
+int df_test_timestep_embedding(const float* t_dev, float* out_dev, int N, int dim, void* stream);
+int df_test_timestep_embedding_b16(const float* t_dev, int t_B, uint16_t* out_dev, int N, int dim, void* stream);
+int df_test_pack_latent(const float* x_dev, uint16_t* out_dev, int B, int C, int HW, int cpad, int rep, float in_scale,
+                        const float* wpq_dev, const float* bpq_dev, void* stream);
+int df_test_pack_latent_bcast(const float* x_dev, uint16_t* out_dev, int B, int C, int HW, int cpad, int rep, const float* src_dev,
+                              float* dst_dev, int rows, int n, void* stream);
+int df_test_bcast_rows(const float* src_dev, float* dst_dev, int rows, int n, void* stream);
+int df_test_cast_bf16(const float* x_dev, uint16_t* out_dev, int64_t n, void* stream);
+int df_test_cast_bf16_2d(const float* x_dev, int ld, uint16_t* out_dev, int64_t rows, int C, void* stream);
+int df_test_avgpool(const float* x_dev, float* out_dev, int N, int HW, int C, void* stream);
+int df_test_pack_conv_weight(const float* w_dev, uint16_t* out_dev, int O, int I, int KH, int KW, int Ipad, void* stream);
+int df_test_pack_conv_skip(const float* w_dev, const float* ws_dev, uint16_t* out_dev, int O, int I, int I2, void* stream);
+int df_test_pack_geglu(const float* w_dev, const float* b_dev, uint16_t* wout_dev, float* bout_dev, int half_rows, int K, void* stream);
+int df_test_pack_ln_linear(const float* w_dev, const float* bias_dev, const float* gamma_dev, const float* beta_dev, uint16_t* wout_dev,
+                           float* cs_dev, float* bb_dev, int rows, int K, int row_off, int geglu_half, void* stream);
+int df_test_grad_scale_per_sample(float* x_dev, const float* prob_dev, int N, int64_t per, void* stream);
+int df_test_stem_im2col(const float* x_dev, uint16_t* out_dev, int F, int H, int W, int OH, int OW, int KP, void* stream);
+int df_test_maxpool3x3s2(const uint16_t* x_dev, uint16_t* out_dev, int F, int H, int W, int OH, int OW, int C, void* stream);
+int df_test_subsample2(const uint16_t* x_dev, uint16_t* out_dev, int F, int H, int W, int C, void* stream);
+int df_test_tcat3(const uint16_t* x_dev, uint16_t* out_dev, int F, int T, int HW, int C, void* stream);
+int df_test_pack_conv3d_bn(const float* w_dev, const float* gamma_dev, const float* beta_dev, const float* mean_dev, const float* var_dev,
+                           float eps, uint16_t* out_dev, float* bias_dev, int O, int I, int KT, int KH, int KW, int KP, void* stream);
+int df_test_maxpool_time(const float* x_dev, float* out_dev, int B, int T, int C, int k, void* stream);
+int df_test_l2norm_rows(float* x_dev, int rows, int C, void* stream);
 /* One GEMM with any GemmParams epilogue (csrc/gemm.h) switched on, on a caller-chosen (tile, split-K, batch, gm): the tests of the
  * autotuner's search space.  `size` must be sizeof(df_test_gemm_desc).  Geometry: conv == 0 linear, A [M][lda] (lda 0 = K);
  * conv == 1 a pad-1 3x3 conv, A NHWC [NB][H][Wd][Cin], W [N][9][Cin], M = NB * OH * OW.  Null / zero fields are off.  ldc 0 = N.
