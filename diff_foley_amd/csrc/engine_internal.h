@@ -450,6 +450,9 @@ std::string keyf(const char* fmt, ...);
 struct TuneChoice { int tile, sk, gm; };
 std::map<std::string, TuneChoice>& tune_cache();
 extern bool g_tune_imported;       // set by df_tune_cache_import (see engine_tune.hip)
+// "M_N_K_taps_stride_ups_batch_geglu_eEPI": the GEMM class a tuned choice belongs to (defer: the plan leaves its split-K slabs to the
+// next GroupNorm).  The only place the EPI bits are assigned; df_test_gemm_key exposes it to the tests.
+std::string tune_key(const GemmParams& g, int batch, bool defer);
 void apply_tune_cache(Plan* pl);
 void autotune_plan(df_ctx* c, Plan* pl, hipStream_t s);
 

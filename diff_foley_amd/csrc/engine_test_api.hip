@@ -68,8 +68,8 @@ int df_test_gemm_dual(const uint16_t* A, const uint16_t* A2, const uint16_t* W, 
   });
 }
 
-// Every GemmParams epilogue feature on a caller-chosen (tile, split-K, batch, gm): tests/test_gemm_epilogues_gpu.py walks the
-// autotuner's whole search space with it.
+// Every GemmParams operand form and epilogue feature on a caller-chosen (tile, split-K, batch, gm): tests/test_gemm_epilogues_gpu.py
+// and tests/test_gemm_forms_gpu.py walk the autotuner's whole search space with it.
 static void test_gemm_params(const df_test_gemm_desc* d, GemmParams& g) {
   if (!d) fail("df_test_gemm: null descriptor");
   if (d->size != (int64_t)sizeof(df_test_gemm_desc))
@@ -77,18 +77,36 @@ static void test_gemm_params(const df_test_gemm_desc* d, GemmParams& g) {
          sizeof(df_test_gemm_desc));
   const bf16_t* A = (const bf16_t*)d->A;
   const bf16_t* W = (const bf16_t*)d->W;
-  if (d->conv) {
+  if (d->conv == 2) {        // phase-decomposed upsample conv: W is the packed [2][2][N][2][2][Cin] operand
+    if (d->ups || d->zstuff || d->stride > 1) fail("df_test_gemm: conv 2 takes neither ups / zstuff nor a stride");
+    g = Builder::gp_conv3_ups4(A, d->NB, d->H, d->Wd, d->Cin, W, d->N);
+  } else if (d->conv) {
+    if (d->conv != 1) fail("df_test_gemm: conv %d", d->conv);
     if (d->stride != 1 && d->stride != 2) fail("df_test_gemm: conv stride %d", d->stride);
-    g = Builder::gp_conv3(A, d->NB, d->H, d->Wd, d->Cin, W, d->N, d->stride, 0);
+    if (d->zstuff && !d->ups) fail("df_test_gemm: zstuff without ups");
+    if (d->ups && d->stride != 1) fail("df_test_gemm: ups with stride %d", d->stride);
+    g = Builder::gp_conv3(A, d->NB, d->H, d->Wd, d->Cin, W, d->N, d->stride, d->ups ? 1 : 0);
+    g.zstuff = d->zstuff ? 1 : 0;
   } else {
+    if (d->ups || d->zstuff) fail("df_test_gemm: ups / zstuff on a linear GEMM");
     g = Builder::gp_linear(A, d->M, d->K, W, d->N);
     if (d->lda > 0) {
       g.lda = d->lda;
       g.a_bytes = Builder::op_bytes((size_t)d->M * d->lda * 2);
     }
   }
-  g.C = d->C; g.ldc = d->ldc > 0 ? d->ldc : g.N; g.out_bf16 = d->out_operand ? 1 : 0;
-  g.a_bs = d->a_bs; g.w_bs = d->w_bs; g.c_bs = d->c_bs; g.res_bs = d->res_bs;
+  if (d->Cin2 > 0 || d->A2) {     // a second operand tensor for the last Cin2 K columns, sized as the builder sizes it
+    if (d->Cin2 <= 0 || d->lda2 < d->Cin2) fail("df_test_gemm: A2 with Cin2 %d / lda2 %d", d->Cin2, d->lda2);
+    g.A2 = (const bf16_t*)d->A2; g.lda2 = d->lda2; g.Cin2 = d->Cin2;
+    g.a2_bytes = Builder::op_bytes(((size_t)(g.M - 1) * d->lda2 + d->Cin2) * 2);
+    g.K += d->Cin2;
+    g.w_bytes = Builder::op_bytes((size_t)g.N * g.K * 2);
+  }
+  g.geglu = d->geglu ? 1 : 0;
+  g.vt = (bf16_t*)d->vt; g.vt_col0 = d->vt_col0; g.vt_T = d->vt_T; g.ldvt = d->ldvt;
+  g.C = d->C; g.ldc = d->ldc > 0 ? d->ldc : (g.geglu ? g.N / 2 : g.N); g.out_bf16 = d->out_operand ? 1 : 0;
+  g.a_bs = d->a_bs; g.c_bs = d->c_bs; g.res_bs = d->res_bs;
+  if (d->conv != 2) g.w_bs = d->w_bs;      // phase-decomposed: the builder's stride between the four phases' weights stays
   g.alpha = d->alpha;
   g.bias = d->bias;
   g.rowbias = d->rowbias; g.ld_rowbias = d->ld_rowbias; g.rows_per_sample = d->rows_per_sample; g.rowbias_mode = d->rowbias_mode;
@@ -103,6 +121,9 @@ static void test_gemm_params(const df_test_gemm_desc* d, GemmParams& g) {
   g.defer_reduce = d->defer_reduce;
   g.gm = d->gm;
   g.splitk = d->splitk > 1 ? d->splitk : 1;
+  // the wide GEGLU tiles read a 320-column packing that df_test_gemm_ex makes per call; for the host-only queries it is "there"
+  // exactly when its three sources are
+  if (g.geglu && g.N % 320 == 0) { g.W_w320 = W; g.cs_w320 = g.ln_cs; g.bias_w320 = g.bias; }
 }
 
 int df_test_gemm_valid(const df_test_gemm_desc* d, int tile, int batch, int splitk) {
@@ -111,6 +132,21 @@ int df_test_gemm_valid(const df_test_gemm_desc* d, int tile, int batch, int spli
     GemmParams g;
     test_gemm_params(d, g);
     return gemm_tile_valid(g, tile, batch, splitk) ? 1 : 0;
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return -1;
+  }
+}
+
+int df_test_gemm_key(const df_test_gemm_desc* d, int batch, char* buf, int n) {
+  std::lock_guard<std::recursive_mutex> hold(g_api_lock);
+  try {
+    GemmParams g;
+    test_gemm_params(d, g);
+    const std::string key = tune_key(g, batch > 1 ? batch : 1, d->defer_reduce != 0);
+    if (!buf || n <= (int)key.size()) fail("df_test_gemm_key: buffer of %d bytes for a key of %zu", n, key.size());
+    memcpy(buf, key.c_str(), key.size() + 1);
+    return 0;
   } catch (const std::exception& e) {
     g_err = e.what();
     return -1;
@@ -136,8 +172,28 @@ int df_test_gemm_ex(const df_test_gemm_desc* d, void* stream) {
     const int batch = d->batch > 1 ? d->batch : 1;
     if (g.K % 64 != 0) fail("df_test_gemm: K %d is not a multiple of 64", g.K);
     if (d->defer_reduce && g.splitk < 2) fail("df_test_gemm: defer_reduce needs split-K");
-    const size_t slab_bytes = (size_t)g.splitk * g.M * g.N * 4;
+    const size_t slab_bytes = (size_t)g.splitk * g.M * g.N * 4 * (g.taps == 4 ? 4 : 1);     // phase-decomposed: four slabs per split
     if (g.splitk > 1) g.partial = test_partial(slab_bytes);
+    if (gemm_tile_is_wgeglu(d->tile) && g.geglu) {      // the wide tiles read the 320-column packing: permuted here, on every call
+      if (g.N % 320 != 0 || !g.ln_cs || !g.bias) fail("tile %d: N = %d is not a multiple of 320, or no column sums / bias", d->tile, g.N);
+      static void* buf = nullptr;
+      static size_t cap = 0;
+      const size_t wb = ((size_t)g.N * g.K * 2 + 255) & ~(size_t)255, need = wb + (size_t)g.N * 8 + 512;
+      if (need > cap) {
+        if (buf) {
+          HIPCHK(hipDeviceSynchronize());
+          HIPCHK(hipFree(buf));
+          buf = nullptr; cap = 0;
+        }
+        HIPCHK(hipMalloc(&buf, need));
+        cap = need;
+      }
+      uint16_t* w3 = (uint16_t*)buf;
+      float* cs3 = (float*)((char*)buf + wb);
+      float* bb3 = cs3 + g.N;
+      HIPCHK(launch_pack_w320(g.W, g.ln_cs, g.bias, w3, cs3, bb3, g.N, g.K, (hipStream_t)stream));
+      g.W_w320 = w3; g.cs_w320 = cs3; g.bias_w320 = bb3;
+    }
     const hipError_t e = launch_gemm(g, d->tile, batch, (hipStream_t)stream);
     if (e == hipErrorInvalidValue)
       fail("launch_gemm refused tile %d / split-K %d / batch %d (%dx%dx%d)", d->tile, g.splitk, batch, g.M, g.N, g.K);

@@ -12,15 +12,16 @@ DFE_NAMESPACE {
 namespace {
 struct TuneCand { int tile, sk; float iso_ms; double situ_ms; };
 
-static std::string tune_key(const Op& o) {
-  const GemmParams& g = o.gp;
+}  // namespace
+
+std::string tune_key(const GemmParams& g, int batch, bool defer) {
   char key[160];
   const int epi = (g.silu ? 128 : 0) | (g.ln_stats ? 1 : 0) | (g.stats ? 2 : 0) | (g.vt ? 4 : 0) | (g.aux ? 8 : 0) | (g.res ? 16 : 0) | (g.Cin2 ? 32 : 0) |
-                  (o.defer ? 64 : 0) | (g.dup_rows ? 256 : 0);
-  snprintf(key, sizeof key, "%d_%d_%d_%d_%d_%d_%d_%d_e%d", g.M, g.N, g.K, g.taps, g.stride, g.ups, o.batch, g.geglu, epi);
+                  (defer ? 64 : 0) | (g.dup_rows ? 256 : 0);
+  snprintf(key, sizeof key, "%d_%d_%d_%d_%d_%d_%d_%d_e%d", g.M, g.N, g.K, g.taps, g.stride, g.ups, batch, g.geglu, epi);
   return key;
 }
-}  // namespace
+static std::string tune_key(const Op& o) { return tune_key(o.gp, o.batch, o.defer); }
 
 std::map<std::string, TuneChoice>& tune_cache() {
   static std::map<std::string, TuneChoice> m;

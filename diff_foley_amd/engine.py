@@ -39,7 +39,9 @@ class GemmDesc(C.Structure):
         ("ld_aux", C.c_int), ("stats", C.c_void_p), ("stats_slots", C.c_int), ("ln_stats", C.c_void_p), ("ln_slots", C.c_int),
         ("ln_C", C.c_int), ("ln_eps", C.c_float), ("ln_cs", C.c_void_p), ("w_rows", C.c_int), ("sm_w", C.c_int),
         ("sm_valid", C.c_int), ("dup_rows", C.c_int), ("no_c_store", C.c_int), ("store_nchw", C.c_int), ("hw_out", C.c_int),
-        ("cfg_out", C.c_void_p), ("cfg_scale", C.c_float), ("defer_reduce", C.c_int), ("slabs_out", C.c_void_p)]
+        ("cfg_out", C.c_void_p), ("cfg_scale", C.c_float), ("defer_reduce", C.c_int), ("slabs_out", C.c_void_p),
+        ("ups", C.c_int), ("zstuff", C.c_int), ("A2", C.c_void_p), ("lda2", C.c_int), ("Cin2", C.c_int), ("geglu", C.c_int),
+        ("vt", C.c_void_p), ("vt_col0", C.c_int), ("vt_T", C.c_int), ("ldvt", C.c_int)]
 
     def __init__(self, **kw):
         kw.setdefault("alpha", 1.0)
@@ -187,6 +189,7 @@ _SIGS = {
     "df_test_conv3x3_bwd_data": [C.c_void_p] * 5 + [C.c_int] * 8 + [C.c_void_p],
     "df_test_gemm_ex": [C.POINTER(GemmDesc), C.c_void_p],
     "df_test_gemm_valid": [C.POINTER(GemmDesc), C.c_int, C.c_int, C.c_int],
+    "df_test_gemm_key": [C.POINTER(GemmDesc), C.c_int, C.c_char_p, C.c_int],
     "df_test_gemm_tile_info": [C.c_int, C.POINTER(GemmTile)],
     "df_test_xattn_chain": [C.c_void_p] * 10 + [C.c_int] * 6 + [C.c_void_p] * 10 + [C.c_int, C.c_int, C.c_void_p],
     "df_test_pack_ffproj": [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p],

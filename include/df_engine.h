@@ -397,10 +397,23 @@ typedef struct df_test_gemm_desc {
   int dup_rows, no_c_store, store_nchw, hw_out;
   float* cfg_out; float cfg_scale;
   int defer_reduce; float* slabs_out;
+  /* operand side.  conv == 1 with ups (+ zstuff): the conv runs on the nearest-x2 (zero-stuffed) input, M = NB * 2H * 2Wd.
+   * conv == 2: the phase-decomposed upsample conv, W the packed [2][2][N][2][2][Cin] operand, M = NB * H * Wd rows of the GEMM
+   * (C holds the 2H x 2Wd map).  A2 / lda2 / Cin2: a second operand tensor for the last Cin2 K columns -- conv: the folded 1x1
+   * skip, K = 9 Cin + Cin2; linear: K = K + Cin2 (d->K counts A's columns only).  geglu: (32 x | 32 gate) column groups, output
+   * width N / 2; the wide tiles' 320-column packing is made inside the entry on every call.  vt: columns >= vt_col0 are stored
+   * transposed per sample of vt_T rows, [M / vt_T][N - vt_col0][ldvt] operand type. */
+  int ups, zstuff;
+  const void* A2; int lda2, Cin2;
+  int geglu;
+  void* vt; int vt_col0, vt_T, ldvt;
 } df_test_gemm_desc;
 int df_test_gemm_ex(const df_test_gemm_desc* d, void* stream);
 /* gemm_tile_valid(d, tile, batch, splitk): 1 / 0, or -1 (message in df_last_error) for a malformed descriptor.  Host only. */
 int df_test_gemm_valid(const df_test_gemm_desc* d, int tile, int batch, int splitk);
+/* The tune-cache key of the descriptor's GEMM (csrc/engine_tune.hip tune_key: M_N_K_taps_stride_ups_batch_geglu_eEPI; the deferred-reduce
+ * bit from d->defer_reduce), NUL-terminated into buf[n].  Returns 0, or -1 (message in df_last_error).  Host only. */
+int df_test_gemm_key(const df_test_gemm_desc* d, int batch, char* buf, int n);
 /* Row `tile` of the GEMM tile table (csrc/gemm_tiles.def): what a tile id of the plan tables and tune caches means.  `size` must be
  * sizeof(df_test_gemm_tile).  family: 0 generic, 1 halo conv, 2 producer-specialised, 3 persistent GEGLU, 4 wide GEGLU, 5 retired
  * (id reserved, never valid).  dma_threads: the threads that issue DMA requests; ring: depth of the LDS operand rings (halo: of the

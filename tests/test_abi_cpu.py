@@ -71,6 +71,55 @@ def test_gemm_desc_binding_matches_the_build():
         assert b"descriptor" in L.df_last_error()
 
 
+def test_gemm_desc_operand_fields_answer_on_the_host():
+    """One positive and one negative df_test_gemm_valid query per operand-side field of df_test_gemm_desc, and the tune-cache key
+    (df_test_gemm_key) of each form."""
+    import ctypes as C
+    one = (C.c_float * 4096)()
+    p = C.addressof(one)
+    for prec in ("bf16", "fp16"):
+        L = E.lib(prec)
+        valid = lambda d, t, sk=1, batch=1: L.df_test_gemm_valid(C.byref(d), t, batch, sk)
+
+        def key(d, batch=1):
+            buf = C.create_string_buffer(160)
+            assert L.df_test_gemm_key(C.byref(d), batch, buf, 160) == 0, L.df_last_error()
+            return buf.value.decode()
+        # ups + zstuff: MODE 2, the generic tiles that have it; never a halo or a producer-specialised tile
+        z = E.GemmDesc(conv=1, NB=2, H=4, Wd=8, Cin=128, N=64, stride=1, ups=1, zstuff=1, aux=p, ld_aux=64)
+        assert valid(z, 4, 8) == 1 and valid(z, 4, 12) == 0 and valid(z, 25) == 0 and valid(z, 26) == 0
+        assert key(z) == "256_64_1152_9_1_1_1_0_e8"
+        assert valid(E.GemmDesc(conv=1, NB=2, H=4, Wd=8, Cin=128, N=64, stride=1, zstuff=1), 4) == -1      # zstuff without ups
+        # conv == 2: the phase-decomposed upsample conv on tiles 3 / 8 / 9 ..., split-K needs N % 4 == 0 and K / 64 >= 2 sk
+        u = E.GemmDesc(conv=2, NB=2, H=5, Wd=7, Cin=384, N=68)
+        assert valid(u, 3, 12) == 1 and valid(u, 3, 16) == 0 and valid(u, 0) == 0
+        assert key(u) == "70_68_1536_4_1_0_1_0_e0"
+        assert valid(E.GemmDesc(conv=2, NB=2, H=5, Wd=7, Cin=384, N=66), 3, 2) == 0
+        # A2 / lda2 / Cin2, conv: the folded skip runs on the generic tiles and the producer-specialised halo tiles only
+        sk_ = E.GemmDesc(conv=1, NB=2, H=6, Wd=16, Cin=128, N=128, stride=1, A2=p, lda2=64, Cin2=64)
+        assert valid(sk_, 25) == 1 and valid(sk_, 5) == 0 and valid(sk_, 3) == 1
+        assert key(sk_) == "192_128_1216_9_1_0_1_0_e32"
+        odd = E.GemmDesc(conv=1, NB=2, H=6, Wd=16, Cin=128, N=128, stride=1, A2=p, lda2=68, Cin2=64)
+        assert valid(odd, 25) == 0 and valid(odd, 3) == 1        # halo: lda2 % 8
+        assert valid(E.GemmDesc(conv=1, NB=2, H=6, Wd=16, Cin=128, N=128, stride=1, A2=p, lda2=32, Cin2=64), 3) == -1
+        # ... linear: K = K + Cin2 over two operand tensors
+        ff = E.GemmDesc(M=64, N=64, K=256, A2=p, lda2=64, Cin2=64, res=p, ldr=64, defer_reduce=1)
+        assert valid(ff, 3, 2) == 1 and valid(ff, 3, 3) == 0
+        assert key(ff) == "64_64_320_1_1_0_1_0_e112"
+        # geglu: LayerNorm-folded on the persistent and wide tiles; the 10-slot persistent tiles refuse C = 1280
+        ln = dict(ln_stats=p, ln_C=1280, ln_slots=20, ln_cs=p, bias=p, out_operand=1)
+        g = E.GemmDesc(M=64, N=2560, K=1280, geglu=1, A=p, W=p, C=p, **ln)
+        assert valid(g, 31) == 1 and valid(g, 30) == 0 and valid(g, 33) == 1 and valid(g, 3) == 1 and valid(g, 3, 2) == 0
+        assert key(g) == "64_2560_1280_1_1_0_1_1_e1"
+        assert valid(E.GemmDesc(M=64, N=2560, K=1280, A=p, W=p, C=p, **ln), 31) == 0          # the same projection without geglu
+        assert valid(E.GemmDesc(M=64, N=2688, K=1280, geglu=1, A=p, W=p, C=p, **ln), 33) == 0    # N % 320
+        # vt: whole tiles only -- no split-K, vt_col0 a multiple of the tile's BN
+        ln = dict(ln_stats=p, ln_C=320, ln_slots=5, ln_cs=p, bias=p, out_operand=1)
+        v = E.GemmDesc(M=128, N=960, K=320, vt=p, vt_col0=640, vt_T=64, ldvt=72, ldc=648, **ln)
+        assert valid(v, 3) == 1 and valid(v, 3, 2) == 0 and valid(v, 8) == 0
+        assert key(v) == "128_960_320_1_1_0_1_0_e5"
+
+
 # What a GEMM tile id means: the ids are written into the shipped plan tables (diff_foley_amd/tuned/) and into every tune-cache file,
 # so they are a file format.  (display name, family, BM, BN) per id, restated here independently of csrc/gemm_tiles.def.
 _TILE_TABLE = {

@@ -132,6 +132,9 @@ class Case:
         for t in self.outs.values():
             t.fill_(NAN)
 
+    def set_outs(self, d, sk):
+        _set_outs(self, d, sk)
+
     def launch(self, d):
         self.poison()
         rc = lib().df_test_gemm_ex(C.byref(d), stream())
@@ -466,7 +469,7 @@ def _defer_check(cs, tile, sk, own_c):
     M, N = cs.M, cs.N
     slabs = torch.full((sk, M, N), NAN, device="cuda")
     d = cs.desc(tile, sk, 0, defer_reduce=1, slabs_out=slabs.data_ptr())
-    _set_outs(cs, d, sk)
+    cs.set_outs(d, sk)
     rc, msg = cs.launch(d)
     if rc:
         return [f"defer_reduce launch failed: {msg}"]
@@ -477,8 +480,8 @@ def _defer_check(cs, tile, sk, own_c):
     f = cs.f
     rc = lib().df_test_groupnorm_own_slabs(C.c_void_p(cs.gn_x.data_ptr()), N, 2, M // 2, N, C.c_void_p(cs.gn_g.data_ptr()),
                                            C.c_void_p(cs.gn_b.data_ptr()), 1e-5, 1, C.c_void_p(cs.gn_out.data_ptr()),
-                                           C.c_void_p(slabs.data_ptr()), sk, N, C.c_void_p(f["bias"]), C.c_void_p(f["res"]),
-                                           f["ldr"], stream())
+                                           C.c_void_p(slabs.data_ptr()), sk, N, C.c_void_p(f["bias"]), C.c_void_p(f.get("res")),
+                                           f.get("ldr", 0), stream())
     if rc:
         return fails + ["groupnorm_own_slabs: " + lib().df_last_error().decode()]
     if not same_bits(cs.gn_x, own_c):
@@ -504,21 +507,20 @@ def _slices_check(cs, tile, sk, snap):
     return [] if same_bits(cs.outs["C"], snap["C"]) else ["batch launch differs from its single-slice launches"]
 
 
-@pytest.mark.parametrize("case", list(CASES))
-def test_epilogue_on_every_tuner_pair(case):
-    """Every (tile, split-K) pair autotune_plan may launch for this epilogue: float64 reference within the per-element bound,
-    untouched gaps stay NaN, gm walk orders and a repeated launch bit-identical, the batch / dup_rows / defer_reduce invariants."""
+def run_on_every_tuner_pair(case, cs):
+    """The loop of this file and of tests/test_gemm_forms_gpu.py.  Every (tile, split-K) pair autotune_plan may launch for the case:
+    its check (float64 reference within the per-element bound, untouched gaps stay NaN), gm walk orders and a repeated launch
+    bit-identical, the batch / defer_reduce invariants; prints pairs run / refused and the worst error / bound.  -> that worst."""
     t0 = time.time()
-    cs = CASES[case]()
     d = cs.desc(0, 1, 0)
-    _set_outs(cs, d, 1)
+    cs.set_outs(d, 1)
     pairs = tuner_pairs(d, cs.batch)
     assert pairs, f"{case}: the tuner has no pair for this GEMM"
     failures, refused, worst, ran = [], [], 0.0, 0
     for tile, sk in pairs:
         where = f"tile {tile} split-K {sk}"
         d = cs.desc(tile, sk, 0)
-        _set_outs(cs, d, sk)
+        cs.set_outs(d, sk)
         rc, msg = cs.launch(d)
         if rc:
             # the tuner skips a pair launch_gemm refuses (autotune_plan: `continue`); anything else is a failure
@@ -531,7 +533,7 @@ def test_epilogue_on_every_tuner_pair(case):
         snap = {k: t.clone() for k, t in cs.outs.items()}
         for gm in (0,) + GMS:                      # gm 0 again: the same launch repeated
             d = cs.desc(tile, sk, gm)
-            _set_outs(cs, d, sk)
+            cs.set_outs(d, sk)
             rc, msg = cs.launch(d)
             if rc:
                 failures.append(f"{where} gm {gm}: {msg}")
@@ -548,3 +550,11 @@ def test_epilogue_on_every_tuner_pair(case):
           f"{worst:.3f}, {time.time() - t0:.1f} s")
     assert ran > 0, f"{case}: launch_gemm refused every pair the tuner would try:\n" + "\n".join(refused[:10])
     assert not failures, f"{case} [{PREC}]: {len(failures)} failure(s) over {ran} pairs:\n" + "\n".join(failures[:40])
+    return worst
+
+
+@pytest.mark.parametrize("case", list(CASES))
+def test_epilogue_on_every_tuner_pair(case):
+    """Every (tile, split-K) pair autotune_plan may launch for this epilogue: float64 reference within the per-element bound,
+    untouched gaps stay NaN, gm walk orders and a repeated launch bit-identical, the batch / dup_rows / defer_reduce invariants."""
+    run_on_every_tuner_pair(case, CASES[case]())
