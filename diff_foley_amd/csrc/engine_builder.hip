@@ -141,6 +141,13 @@ GemmParams Builder::gp_conv3_ups4(const bf16_t* A, int NB, int H, int Wd, int Ci
   return g;
 }
 
+void Builder::add_a2(GemmParams& g, const bf16_t* A2, int lda2, int Cin2) {
+  g.A2 = A2; g.lda2 = lda2; g.Cin2 = Cin2;
+  g.a2_bytes = op_bytes(((size_t)(g.M - 1) * lda2 + Cin2) * 2);
+  g.K += Cin2;
+  g.w_bytes = op_bytes((size_t)g.N * g.K * 2);
+}
+
 bf16_t* Builder::groupnorm(const F32& x, int NB, const std::string& p, float eps, int silu, bf16_t** raw) {
   bf16_t* o = buf<bf16_t>((size_t)x.rows * x.C);
   bf16_t* r = raw ? buf<bf16_t>((size_t)x.rows * x.C) : nullptr;
@@ -266,9 +273,7 @@ void Builder::resblock(const F32& x, const F32& out, int NB, int H, int Wd, cons
       c->w_conv3_skip(nm(c2), nm(skip), &w, &bsum);
       g.W = w;
       g.bias = bsum;
-      g.A2 = xraw; g.lda2 = cin; g.Cin2 = cin; g.a2_bytes = op_bytes((size_t)M * cin * 2);
-      g.K = 9 * cout + cin;
-      g.w_bytes = op_bytes((size_t)cout * g.K * 2);
+      add_a2(g, xraw, cin, cin);
     } else { g.res = x.p; g.ldr = x.ld; }
     attach_aux(g, M, cout);
     g.dup_rows = dup_rows;       // CFG prefix: this block ran on one half of the batch, its output feeds both
@@ -439,9 +444,7 @@ void Builder::spatial_transformer(const F32& x, const F32& out, int NB, int T, c
     const float* bsum;
     c->w_ffproj(nm(tb + ".ff.net.2"), nm(p + ".proj_out"), &w, &bsum);
     GemmParams g = gp_linear(gl, M, 4 * C, w, C);
-    g.K = 5 * C;
-    g.w_bytes = op_bytes((size_t)C * 5 * C * 2);
-    g.A2 = xb; g.lda2 = C; g.Cin2 = C; g.a2_bytes = op_bytes((size_t)M * C * 2);
+    add_a2(g, xb, C, C);
     out_f32(g, out.p, out.ld);
     g.bias = bsum;
     g.res = x.p; g.ldr = x.ld;

@@ -393,6 +393,9 @@ struct Builder {
   // nearest-x2 upsample + conv3x3 as four 2x2-tap convs (one per output phase) over the INPUT-resolution map: rows = input
   // pixels, K = 4 Cin, one weight matrix per phase (w_bs), output rows = the x2 map (the kernel scatters by phase)
   static GemmParams gp_conv3_ups4(const bf16_t* A, int NB, int H, int Wd, int Cin, const bf16_t* W4, int Cout);
+  // a second operand tensor A2 [M][lda2] for Cin2 more K columns behind g's own (the folded 1x1 skip of a conv, the residual-stream
+  // half of st.ffproj): K grows by Cin2, and W -- [N][K] over the whole K -- is sized again
+  static void add_a2(GemmParams& g, const bf16_t* A2, int lda2, int Cin2);
   static void out_f32(GemmParams& g, float* C, int ldc) { g.C = C; g.ldc = ldc; g.out_bf16 = 0; }
   static void out_b16(GemmParams& g, bf16_t* C, int ldc) { g.C = C; g.ldc = ldc; g.out_bf16 = 1; }
 

@@ -21,55 +21,8 @@ static float* test_partial(size_t bytes) {
   return buf;
 }
 
-int df_test_gemm(const uint16_t* A, const uint16_t* W, float* C, int M, int N, int K, int tile, int splitk, void* stream) {
-  return guard([&] {
-    GemmParams g = Builder::gp_linear(A, M, K, W, N);
-    Builder::out_f32(g, C, N);
-    g.dbg = getenv("DF_GEMM_DBG") ? atoi(getenv("DF_GEMM_DBG")) : 0;
-    g.splitk = splitk;
-    if (splitk > 1) g.partial = test_partial((size_t)splitk * M * N * 4);
-    else if (g.dbg & 64) g.partial = test_partial((size_t)4096 * 32 * 8);      // per-block clock stamps (tools/gemm_stamps.py)
-    HIPCHK(launch_gemm(g, tile, 1, (hipStream_t)stream));
-  });
-}
-
-// The GEMM with its simple epilogue features switched on: bias, residual, activation (1 = SiLU, 2 = ReLU), fp32 or
-// operand-type output, with and without split-K -- every tile must give the same answer for every combination.
-int df_test_gemm_epi(const uint16_t* A, const uint16_t* W, const float* bias, const float* res, void* C, int M, int N, int K,
-                     int act, int out_operand, int tile, int splitk, void* stream) {
-  return guard([&] {
-    GemmParams g = Builder::gp_linear(A, M, K, W, N);
-    if (out_operand) Builder::out_b16(g, (bf16_t*)C, N);
-    else Builder::out_f32(g, (float*)C, N);
-    g.bias = bias;
-    if (res) { g.res = res; g.ldr = N; }
-    g.silu = act == 1;
-    g.relu = act == 2;
-    g.splitk = splitk;
-    if (splitk > 1) g.partial = test_partial((size_t)splitk * M * N * 4);
-    if (!gemm_tile_valid(g, tile, 1, splitk)) fail("tile %d / split-K %d refused this problem", tile, splitk);
-    HIPCHK(launch_gemm(g, tile, 1, (hipStream_t)stream));
-  });
-}
-
-// C = [A | A2] W^T with the K columns split over two operand tensors (the merged FF2 + proj_out GEMM of the SpatialTransformer).
-int df_test_gemm_dual(const uint16_t* A, const uint16_t* A2, const uint16_t* W, float* C, int M, int N, int K1, int K2, int tile,
-                      int splitk, void* stream) {
-  return guard([&] {
-    GemmParams g = Builder::gp_linear(A, M, K1, W, N);
-    g.K = K1 + K2;
-    g.w_bytes = Builder::op_bytes((size_t)N * (K1 + K2) * 2);
-    g.A2 = A2; g.lda2 = K2; g.Cin2 = K2; g.a2_bytes = Builder::op_bytes((size_t)M * K2 * 2);
-    Builder::out_f32(g, C, N);
-    g.splitk = splitk;
-    if (splitk > 1) g.partial = test_partial((size_t)splitk * M * N * 4);
-    if (!gemm_tile_valid(g, tile, 1, splitk)) fail("tile %d / split-K %d refused this problem", tile, splitk);
-    HIPCHK(launch_gemm(g, tile, 1, (hipStream_t)stream));
-  });
-}
-
-// Every GemmParams operand form and epilogue feature on a caller-chosen (tile, split-K, batch, gm): tests/test_gemm_epilogues_gpu.py
-// and tests/test_gemm_forms_gpu.py walk the autotuner's whole search space with it.
+// Test input -> GemmParams: every operand form and epilogue feature the plans use.  The one translation; run_test_gemm below is the
+// one launch behind the eight single-GEMM entry points.
 static void test_gemm_params(const df_test_gemm_desc* d, GemmParams& g) {
   if (!d) fail("df_test_gemm: null descriptor");
   if (d->size != (int64_t)sizeof(df_test_gemm_desc))
@@ -97,10 +50,7 @@ static void test_gemm_params(const df_test_gemm_desc* d, GemmParams& g) {
   }
   if (d->Cin2 > 0 || d->A2) {     // a second operand tensor for the last Cin2 K columns, sized as the builder sizes it
     if (d->Cin2 <= 0 || d->lda2 < d->Cin2) fail("df_test_gemm: A2 with Cin2 %d / lda2 %d", d->Cin2, d->lda2);
-    g.A2 = (const bf16_t*)d->A2; g.lda2 = d->lda2; g.Cin2 = d->Cin2;
-    g.a2_bytes = Builder::op_bytes(((size_t)(g.M - 1) * d->lda2 + d->Cin2) * 2);
-    g.K += d->Cin2;
-    g.w_bytes = Builder::op_bytes((size_t)g.N * g.K * 2);
+    Builder::add_a2(g, (const bf16_t*)d->A2, d->lda2, d->Cin2);
   }
   g.geglu = d->geglu ? 1 : 0;
   g.vt = (bf16_t*)d->vt; g.vt_col0 = d->vt_col0; g.vt_T = d->vt_T; g.ldvt = d->ldvt;
@@ -121,7 +71,7 @@ static void test_gemm_params(const df_test_gemm_desc* d, GemmParams& g) {
   g.defer_reduce = d->defer_reduce;
   g.gm = d->gm;
   g.splitk = d->splitk > 1 ? d->splitk : 1;
-  // the wide GEGLU tiles read a 320-column packing that df_test_gemm_ex makes per call; for the host-only queries it is "there"
+  // the wide GEGLU tiles read a 320-column packing that run_test_gemm makes per call; for the host-only queries it is "there"
   // exactly when its three sources are
   if (g.geglu && g.N % 320 == 0) { g.W_w320 = W; g.cs_w320 = g.ln_cs; g.bias_w320 = g.bias; }
 }
@@ -165,41 +115,162 @@ int df_test_gemm_tile_info(int tile, df_test_gemm_tile* out) {
   return 0;
 }
 
+// The wide GEGLU tiles read the 320-column packing of (W, column sums, bias): permuted here into a grow-only scratch, on every
+// call -- unless `keep` (timing tools) and the packing in the scratch was made from this W by the call before.
+static void test_pack_w320(GemmParams& g, bool keep, hipStream_t s) {
+  static void* buf = nullptr;
+  static size_t cap = 0;
+  static const void* packed_from = nullptr;
+  const size_t wb = ((size_t)g.N * g.K * 2 + 255) & ~(size_t)255, need = wb + (size_t)g.N * 8 + 512;
+  if (need > cap) {
+    if (buf) {
+      HIPCHK(hipDeviceSynchronize());
+      HIPCHK(hipFree(buf));
+      buf = nullptr; cap = 0;
+    }
+    packed_from = nullptr;
+    HIPCHK(hipMalloc(&buf, need));
+    cap = need;
+  }
+  uint16_t* w3 = (uint16_t*)buf;
+  float* cs3 = (float*)((char*)buf + wb);
+  float* bb3 = cs3 + g.N;
+  if (!keep || packed_from != (const void*)g.W) HIPCHK(launch_pack_w320(g.W, g.ln_cs, g.bias, w3, cs3, bb3, g.N, g.K, s));
+  packed_from = (const void*)g.W;
+  g.W_w320 = w3; g.cs_w320 = cs3; g.bias_w320 = bb3;
+}
+
+// What the single-GEMM entry points differ in once their descriptor is filled.
+struct TestGemmOpts {
+  int dbg = 0;                   // GemmParams::dbg (tools: timing switches, bit 6 = per-block clock stamps into the shared scratch)
+  bool require_valid = false;    // ask gemm_tile_valid first (launch_gemm alone does not apply it to the generic tiles)
+  bool keep_w320 = false;        // wide GEGLU tiles: reuse the packing the previous call made from the same W
+};
+static int env_gemm_dbg() { return getenv("DF_GEMM_DBG") ? atoi(getenv("DF_GEMM_DBG")) : 0; }
+
+// descriptor -> GemmParams -> launch: everything the eight single-GEMM entry points below do on the device
+static void run_test_gemm(const df_test_gemm_desc& d, const TestGemmOpts& o, hipStream_t s) {
+  GemmParams g;
+  test_gemm_params(&d, g);
+  const int batch = d.batch > 1 ? d.batch : 1;
+  // as Builder::gemm: the K loop of every kernel walks whole 64-element steps, a ragged K would silently drop its tail
+  if (g.K % 64 != 0 || (g.taps != 1 && g.Cin % 64 != 0))
+    fail("df_test_gemm (%dx%dx%d, Cin %d): the contraction length must be a multiple of 64", g.M, g.N, g.K, g.Cin);
+  if (d.defer_reduce && g.splitk < 2) fail("df_test_gemm: defer_reduce needs split-K");
+  g.dbg = o.dbg;
+  if (o.require_valid && !gemm_tile_valid(g, d.tile, batch, g.splitk)) fail("tile %d / split-K %d refused this problem", d.tile, g.splitk);
+  const size_t slab_bytes = (size_t)g.splitk * g.M * g.N * 4 * (g.taps == 4 ? 4 : 1);     // phase-decomposed: four slabs per split
+  if (g.splitk > 1) g.partial = test_partial(slab_bytes);
+  else if (g.dbg & 64) g.partial = test_partial((size_t)4096 * 32 * 8);      // per-block clock stamps (df_test_scratch_read)
+  if (gemm_tile_is_wgeglu(d.tile) && g.geglu) {
+    if (g.N % 320 != 0 || !g.ln_cs || !g.bias) fail("tile %d: N = %d is not a multiple of 320, or no column sums / bias", d.tile, g.N);
+    test_pack_w320(g, o.keep_w320, s);
+  }
+  const hipError_t e = launch_gemm(g, d.tile, batch, s);
+  if (e == hipErrorInvalidValue)
+    fail("launch_gemm refused tile %d / split-K %d / batch %d (%dx%dx%d): %s", d.tile, g.splitk, batch, g.M, g.N, g.K,
+         hipGetErrorString(e));
+  HIPCHK(e);
+  if (d.defer_reduce && d.slabs_out) HIPCHK(hipMemcpyAsync(d.slabs_out, g.partial, slab_bytes, hipMemcpyDeviceToDevice, s));
+}
+
 int df_test_gemm_ex(const df_test_gemm_desc* d, void* stream) {
   return guard([&] {
-    GemmParams g;
-    test_gemm_params(d, g);
-    const int batch = d->batch > 1 ? d->batch : 1;
-    if (g.K % 64 != 0) fail("df_test_gemm: K %d is not a multiple of 64", g.K);
-    if (d->defer_reduce && g.splitk < 2) fail("df_test_gemm: defer_reduce needs split-K");
-    const size_t slab_bytes = (size_t)g.splitk * g.M * g.N * 4 * (g.taps == 4 ? 4 : 1);     // phase-decomposed: four slabs per split
-    if (g.splitk > 1) g.partial = test_partial(slab_bytes);
-    if (gemm_tile_is_wgeglu(d->tile) && g.geglu) {      // the wide tiles read the 320-column packing: permuted here, on every call
-      if (g.N % 320 != 0 || !g.ln_cs || !g.bias) fail("tile %d: N = %d is not a multiple of 320, or no column sums / bias", d->tile, g.N);
-      static void* buf = nullptr;
-      static size_t cap = 0;
-      const size_t wb = ((size_t)g.N * g.K * 2 + 255) & ~(size_t)255, need = wb + (size_t)g.N * 8 + 512;
-      if (need > cap) {
-        if (buf) {
-          HIPCHK(hipDeviceSynchronize());
-          HIPCHK(hipFree(buf));
-          buf = nullptr; cap = 0;
-        }
-        HIPCHK(hipMalloc(&buf, need));
-        cap = need;
-      }
-      uint16_t* w3 = (uint16_t*)buf;
-      float* cs3 = (float*)((char*)buf + wb);
-      float* bb3 = cs3 + g.N;
-      HIPCHK(launch_pack_w320(g.W, g.ln_cs, g.bias, w3, cs3, bb3, g.N, g.K, (hipStream_t)stream));
-      g.W_w320 = w3; g.cs_w320 = cs3; g.bias_w320 = bb3;
-    }
-    const hipError_t e = launch_gemm(g, d->tile, batch, (hipStream_t)stream);
-    if (e == hipErrorInvalidValue)
-      fail("launch_gemm refused tile %d / split-K %d / batch %d (%dx%dx%d)", d->tile, g.splitk, batch, g.M, g.N, g.K);
-    HIPCHK(e);
-    if (d->defer_reduce && d->slabs_out)
-      HIPCHK(hipMemcpyAsync(d->slabs_out, g.partial, slab_bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    if (!d) fail("df_test_gemm: null descriptor");
+    run_test_gemm(*d, TestGemmOpts{}, (hipStream_t)stream);
+  });
+}
+
+// ---- the fixed-shape entry points: each fills a descriptor and runs it
+static df_test_gemm_desc test_desc(const void* A, const void* W, void* C, int tile, int splitk) {
+  df_test_gemm_desc d{};
+  d.size = sizeof d;
+  d.alpha = 1.f;
+  d.A = A; d.W = W; d.C = C; d.tile = tile; d.splitk = splitk;
+  return d;
+}
+static df_test_gemm_desc test_desc_conv(const void* A, const void* W, void* C, int tile, int splitk, int conv, int NB, int H, int Wd,
+                                        int Cin, int Cout, const float* bias) {
+  df_test_gemm_desc d = test_desc(A, W, C, tile, splitk);
+  d.conv = conv; d.NB = NB; d.H = H; d.Wd = Wd; d.Cin = Cin; d.N = Cout; d.stride = 1; d.bias = bias;
+  return d;
+}
+
+// ungated, DF_GEMM_DBG from the environment: the tools time (tile, split-K) pairs the tuner would not pick
+int df_test_gemm(const uint16_t* A, const uint16_t* W, float* C, int M, int N, int K, int tile, int splitk, void* stream) {
+  return guard([&] {
+    df_test_gemm_desc d = test_desc(A, W, C, tile, splitk);
+    d.M = M; d.N = N; d.K = K;
+    run_test_gemm(d, {env_gemm_dbg(), false, false}, (hipStream_t)stream);
+  });
+}
+
+// bias, residual, activation (1 = SiLU, 2 = ReLU), fp32 or operand-type output
+int df_test_gemm_epi(const uint16_t* A, const uint16_t* W, const float* bias, const float* res, void* C, int M, int N, int K,
+                     int act, int out_operand, int tile, int splitk, void* stream) {
+  return guard([&] {
+    df_test_gemm_desc d = test_desc(A, W, C, tile, splitk);
+    d.M = M; d.N = N; d.K = K;
+    d.bias = bias;
+    d.res = res; d.ldr = res ? N : 0;
+    d.silu = act == 1; d.relu = act == 2;
+    d.out_operand = out_operand;
+    run_test_gemm(d, {0, true, false}, (hipStream_t)stream);
+  });
+}
+
+// C = [A | A2] W^T with the K columns split over two operand tensors (the merged FF2 + proj_out GEMM of the SpatialTransformer)
+int df_test_gemm_dual(const uint16_t* A, const uint16_t* A2, const uint16_t* W, float* C, int M, int N, int K1, int K2, int tile,
+                      int splitk, void* stream) {
+  return guard([&] {
+    df_test_gemm_desc d = test_desc(A, W, C, tile, splitk);
+    d.M = M; d.N = N; d.K = K1;
+    d.A2 = A2; d.lda2 = K2; d.Cin2 = K2;
+    run_test_gemm(d, {0, true, false}, (hipStream_t)stream);
+  });
+}
+
+// ungated like df_test_gemm (a halo tile's refusal of a map is launch_gemm's own), DF_GEMM_DBG from the environment
+int df_test_conv3x3(const uint16_t* A, const uint16_t* W, const float* bias, float* C, int NB, int H, int Wd, int Cin,
+                    int Cout, int stride, int ups, int tile, int splitk, void* stream) {
+  return guard([&] {
+    df_test_gemm_desc d = test_desc_conv(A, W, C, tile, splitk, 1, NB, H, Wd, Cin, Cout, bias);
+    d.stride = stride; d.ups = ups;
+    run_test_gemm(d, {env_gemm_dbg(), false, false}, (hipStream_t)stream);
+  });
+}
+
+int df_test_conv3x3_skip(const uint16_t* A, const uint16_t* A2, const uint16_t* W, const float* bias, float* C, int NB, int H,
+                         int Wd, int Cin, int Cin2, int Cout, int tile, int splitk, void* stream) {
+  return guard([&] {
+    df_test_gemm_desc d = test_desc_conv(A, W, C, tile, splitk, 1, NB, H, Wd, Cin, Cout, bias);
+    d.A2 = A2; d.lda2 = Cin2; d.Cin2 = Cin2;
+    run_test_gemm(d, {0, true, false}, (hipStream_t)stream);
+  });
+}
+
+// Upsample + conv3x3 through the phase-decomposed form (gemm_m3.hip): W_oihw fp32 [Cout][Cin][3][3] is packed here.
+int df_test_conv3x3_ups4(const uint16_t* A, const float* W_oihw, const float* bias, float* C, uint16_t* w4_scratch, int NB, int H,
+                         int Wd, int Cin, int Cout, int tile, int splitk, void* stream) {
+  return guard([&] {
+    HIPCHK(launch_pack_conv_ups4(W_oihw, w4_scratch, Cout, Cin, Cin, (hipStream_t)stream));
+    const df_test_gemm_desc d = test_desc_conv(A, w4_scratch, C, tile, splitk, 2, NB, H, Wd, Cin, Cout, bias);
+    run_test_gemm(d, {0, true, false}, (hipStream_t)stream);
+  });
+}
+
+// The LayerNorm-folded GEGLU projection alone, on caller-owned operands (timing probes: tools/pgeglu_probe.py).  stats [M][K/64]
+// float2, cs / bias [N1]; dbg = debug switches of the persistent kernel (ffn.hip) or DF_GEMM_DBG of the generic one; its bit 7 is
+// this entry's own: keep the wide tiles' packing made from the same W by the previous call.
+int df_test_geglu(const uint16_t* A, const uint16_t* W, const void* stats, const float* cs, const float* bias, uint16_t* out, int M,
+                  int K, int N1, int tile, int dbg, void* stream) {
+  return guard([&] {
+    df_test_gemm_desc d = test_desc(A, W, out, tile, 1);
+    d.M = M; d.N = N1; d.K = K;
+    d.geglu = 1; d.out_operand = 1;
+    d.ln_stats = stats; d.ln_slots = K / 64; d.ln_C = K; d.ln_eps = 1e-5f; d.ln_cs = cs;
+    d.bias = bias;
+    run_test_gemm(d, {dbg & ~128, true, (dbg & 128) != 0}, (hipStream_t)stream);
   });
 }
 
@@ -320,44 +391,6 @@ int df_test_ln_chain(const uint16_t* A0, const uint16_t* W0, const float* b0, co
   });
 }
 
-// The LayerNorm-folded GEGLU projection alone, on caller-owned operands (timing probes: tools/pgeglu_probe.py).  stats [M][K/64]
-// float2, cs / bias [N1]; dbg = debug switches of the persistent kernel (ffn.hip) or DF_GEMM_DBG of the generic one.
-int df_test_geglu(const uint16_t* A, const uint16_t* W, const void* stats, const float* cs, const float* bias, uint16_t* out, int M,
-                  int K, int N1, int tile, int dbg, void* stream) {
-  return guard([&] {
-    GemmParams g = Builder::gp_linear(A, M, K, W, N1);
-    g.ln_stats = (const float2*)stats; g.ln_slots = K / 64; g.ln_C = K; g.ln_eps = 1e-5f; g.ln_cs = cs;
-    g.bias = bias;
-    Builder::out_b16(g, out, N1 / 2);
-    g.geglu = 1;
-    g.splitk = 1;
-    g.dbg = dbg;
-    if (dbg & 64) g.partial = test_partial((size_t)1024 * 32 * 8);     // per-block clock stamps (read back with df_test_scratch_read)
-    if (gemm_tile_is_wgeglu(tile)) {      // the wide tiles read the 320-column packing: permuted here, per call (test entry)
-      if (N1 % 320 != 0) fail("tile %d: N = %d is not a multiple of 320", tile, N1);
-      static void* buf = nullptr;
-      static size_t cap = 0;
-      const size_t need = (size_t)N1 * K * 2 + (size_t)N1 * 8 + 512;
-      if (need > cap) {
-        if (buf) HIPCHK(hipFree(buf));
-        HIPCHK(hipMalloc(&buf, need));
-        cap = need;
-      }
-      uint16_t* w3 = (uint16_t*)buf;
-      float* cs3 = (float*)((char*)buf + (((size_t)N1 * K * 2 + 255) & ~(size_t)255));
-      float* bb3 = cs3 + N1;
-      static const void* packed_from = nullptr;
-      if (!(dbg & 128) || packed_from != (const void*)W)      // dbg bit 7 (timing tools): keep the packing made from this W by the last call
-        HIPCHK(launch_pack_w320(W, cs, bias, w3, cs3, bb3, N1, K, (hipStream_t)stream));
-      packed_from = (const void*)W;
-      g.dbg = dbg & ~128;
-      g.W_w320 = w3; g.cs_w320 = cs3; g.bias_w320 = bb3;
-    }
-    if (!gemm_tile_valid(g, tile, 1, 1)) fail("tile %d not valid for this GEGLU projection", tile);
-    HIPCHK(launch_gemm(g, tile, 1, (hipStream_t)stream));
-  });
-}
-
 int df_test_scratch_read(void* host, int64_t bytes) {
   return guard([&] {
     HIPCHK(hipDeviceSynchronize());
@@ -428,54 +461,9 @@ int df_test_unet_block(df_ctx* c, const char* prefix, int kind, const float* x, 
   });
 }
 
-int df_test_conv3x3(const uint16_t* A, const uint16_t* W, const float* bias, float* C, int NB, int H, int Wd, int Cin,
-                    int Cout, int stride, int ups, int tile, int splitk, void* stream) {
-  return guard([&] {
-    GemmParams g = Builder::gp_conv3(A, NB, H, Wd, Cin, W, Cout, stride, ups);
-    Builder::out_f32(g, C, Cout);
-    g.bias = bias;
-    g.splitk = splitk;
-    g.dbg = getenv("DF_GEMM_DBG") ? atoi(getenv("DF_GEMM_DBG")) : 0;
-    if (splitk > 1) g.partial = test_partial((size_t)splitk * g.M * g.N * 4);
-    else if (g.dbg & 64) g.partial = test_partial((size_t)4096 * 32 * 8);      // halo kernels: per-block clock stamps
-    HIPCHK(launch_gemm(g, tile, 1, (hipStream_t)stream));
-  });
-}
-
 int df_test_conv3x3_fewout(const uint16_t* A, const uint16_t* W, const float* bias, float* out_nchw, int NB, int H, int Wd, int Cin,
                            int Cout, void* stream) {
   return guard([&] { HIPCHK(launch_conv3x3_fewout(A, W, bias, out_nchw, NB, H, Wd, Cin, Cout, (hipStream_t)stream)); });
-}
-
-int df_test_conv3x3_skip(const uint16_t* A, const uint16_t* A2, const uint16_t* W, const float* bias, float* C, int NB, int H,
-                         int Wd, int Cin, int Cin2, int Cout, int tile, int splitk, void* stream) {
-  return guard([&] {
-    GemmParams g = Builder::gp_conv3(A, NB, H, Wd, Cin, W, Cout, 1, 0);
-    Builder::out_f32(g, C, Cout);
-    g.bias = bias;
-    g.A2 = A2; g.lda2 = Cin2; g.Cin2 = Cin2; g.a2_bytes = Builder::op_bytes((size_t)g.M * Cin2 * 2);
-    g.K = 9 * Cin + Cin2;
-    g.w_bytes = Builder::op_bytes((size_t)Cout * g.K * 2);
-    g.splitk = splitk;
-    if (splitk > 1) g.partial = test_partial((size_t)splitk * g.M * g.N * 4);
-    if (!gemm_tile_valid(g, tile, 1, splitk)) fail("tile %d / split-K %d refused this problem", tile, splitk);
-    HIPCHK(launch_gemm(g, tile, 1, (hipStream_t)stream));
-  });
-}
-
-// Upsample + conv3x3 through the phase-decomposed form (gemm_m3.hip): W_oihw fp32 [Cout][Cin][3][3] is packed here.
-int df_test_conv3x3_ups4(const uint16_t* A, const float* W_oihw, const float* bias, float* C, uint16_t* w4_scratch, int NB, int H,
-                         int Wd, int Cin, int Cout, int tile, int splitk, void* stream) {
-  return guard([&] {
-    HIPCHK(launch_pack_conv_ups4(W_oihw, w4_scratch, Cout, Cin, Cin, (hipStream_t)stream));
-    GemmParams g = Builder::gp_conv3_ups4(A, NB, H, Wd, Cin, w4_scratch, Cout);
-    Builder::out_f32(g, C, Cout);
-    g.bias = bias;
-    g.splitk = splitk;
-    if (splitk > 1) g.partial = test_partial((size_t)splitk * 4 * g.M * g.N * 4);
-    if (!gemm_tile_valid(g, tile, 1, splitk)) fail("tile %d / split-K %d refused this problem", tile, splitk);
-    HIPCHK(launch_gemm(g, tile, 1, (hipStream_t)stream));
-  });
 }
 
 // Which kernel form a shape takes (host only; csrc/kernels.h groupnorm_form / attention_form -- the functions the launchers

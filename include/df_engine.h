@@ -256,6 +256,13 @@ int df_debug_requant(df_ctx* ctx, const char* tag_prefixes);
 int df_debug_saturation_label(df_ctx* ctx, int64_t index, char* buf, int64_t len);
 /* Run ONE op family in isolation for unit tests (see tests/test_kernels_gpu.py). */
 int df_test_scratch_read(void* host, int64_t bytes);     /* the shared scratch of the test entry points (debug stamps) */
+/* df_test_gemm, _gemm_epi, _gemm_dual, df_test_conv3x3, _conv3x3_skip, _conv3x3_ups4 and df_test_geglu are fixed-shape fills of
+ * the df_test_gemm_desc below, run through the one path of df_test_gemm_ex: K (convs: Cin too) must be a multiple of 64, and a refusal
+ * of the launch reads "launch_gemm refused ...: invalid argument".  _gemm_epi, _gemm_dual, _conv3x3_skip, _conv3x3_ups4 and
+ * df_test_geglu ask gemm_tile_valid first ("tile T / split-K S refused this problem"); df_test_gemm and df_test_conv3x3 do not, like
+ * df_test_gemm_ex -- they also take GemmParams::dbg from the environment (DF_GEMM_DBG; bit 6: per-block clock stamps).
+ * df_test_geglu: the LayerNorm-folded GEGLU projection (stats [M][K/64] float2, cs / bias [N1], out operand type [M][N1/2]); dbg goes
+ * to GemmParams::dbg except bit 7, which keeps the wide tiles' 320-column packing made from the same W by the previous call. */
 int df_test_geglu(const uint16_t* A_dev, const uint16_t* W_dev, const void* stats_dev, const float* cs_dev, const float* bias_dev,
                   uint16_t* out_dev, int M, int K, int N1, int tile, int dbg, void* stream);
 int df_test_conv3x3_fewout(const uint16_t* A_nhwc_dev, const uint16_t* W_okki_dev, const float* bias_dev, float* out_nchw_dev, int NB,
