@@ -147,6 +147,7 @@ void run_ops(df_ctx* c, Plan* pl, size_t begin, size_t end, hipStream_t s, const
   for (size_t i = begin; i < end; ++i) {
     Op& o = pl->ops[i];
     hipError_t e;
+    const char* why = nullptr;       // launch_gemm's rule, when it refuses
     (void)hipGetLastError();     // a stale launch-configuration error (e.g. a refused tuning candidate) is not this op's
     if (c->prof_on) {
       if (c->prof_used + 2 > c->prof_ev.size()) {
@@ -163,14 +164,14 @@ void run_ops(df_ctx* c, Plan* pl, size_t begin, size_t end, hipStream_t s, const
       if (o.c_ext) g.C = a.out;
       if (o.cfg_ext && g.splitk > 1) { g.cfg_out = a.out; g.cfg_scale = a.scale; }
       if (o.defer && g.splitk > 1) g.defer_reduce = 1;
-      e = launch_gemm(g, o.tile, o.batch, s);
+      e = launch_gemm(g, o.tile, o.batch, s, &why);
     } else {
       e = o.fn(s, a);
     }
     if (e != hipSuccess) {
       if (o.is_gemm)
-        fail("op %zu (%s: GEMM %dx%dx%d taps %d batch %d tile %d split-K %d) failed: %s", i, o.tag, o.gp.M, o.gp.N, o.gp.K,
-             o.gp.taps, o.batch, o.tile, o.gp.splitk, hipGetErrorString(e));
+        fail("op %zu (%s: GEMM %dx%dx%d taps %d batch %d tile %d split-K %d) failed: %s%s%s%s", i, o.tag, o.gp.M, o.gp.N, o.gp.K,
+             o.gp.taps, o.batch, o.tile, o.gp.splitk, hipGetErrorString(e), why ? " (" : "", why ? why : "", why ? ")" : "");
       fail("op %zu (%s) failed: %s", i, o.tag, hipGetErrorString(e));
     }
     if (c->prof_on) {

@@ -76,16 +76,24 @@ static void test_gemm_params(const df_test_gemm_desc* d, GemmParams& g) {
   if (g.geglu && g.N % 320 == 0) { g.W_w320 = W; g.cs_w320 = g.ln_cs; g.bias_w320 = g.bias; }
 }
 
-int df_test_gemm_valid(const df_test_gemm_desc* d, int tile, int batch, int splitk) {
+// 0: launchable and inside the tuner's split policy;  1: launchable, outside the policy;  2: refused, the rule in buf;  -1: bad descriptor
+int df_test_gemm_why(const df_test_gemm_desc* d, int tile, int batch, int splitk, char* buf, int n) {
   std::lock_guard<std::recursive_mutex> hold(g_api_lock);
   try {
     GemmParams g;
     test_gemm_params(d, g);
-    return gemm_tile_valid(g, tile, batch, splitk) ? 1 : 0;
+    const char* why = gemm_route(g, tile, batch, splitk, nullptr);
+    if (buf && n > 0) snprintf(buf, (size_t)n, "%s", why ? why : "");
+    return why ? 2 : (gemm_split_worth_tuning(g, tile, splitk) ? 0 : 1);
   } catch (const std::exception& e) {
     g_err = e.what();
     return -1;
   }
+}
+
+int df_test_gemm_valid(const df_test_gemm_desc* d, int tile, int batch, int splitk) {
+  const int r = df_test_gemm_why(d, tile, batch, splitk, nullptr, 0);
+  return r < 0 ? -1 : (r == 0 ? 1 : 0);
 }
 
 int df_test_gemm_key(const df_test_gemm_desc* d, int batch, char* buf, int n) {
@@ -143,10 +151,20 @@ static void test_pack_w320(GemmParams& g, bool keep, hipStream_t s) {
 // What the single-GEMM entry points differ in once their descriptor is filled.
 struct TestGemmOpts {
   int dbg = 0;                   // GemmParams::dbg (tools: timing switches, bit 6 = per-block clock stamps into the shared scratch)
-  bool require_valid = false;    // ask gemm_tile_valid first (launch_gemm alone does not apply it to the generic tiles)
+  bool tuner_policy = false;     // also apply the tuner's split policy (gemm_split_worth_tuning); launch_gemm itself refuses what cannot run
   bool keep_w320 = false;        // wide GEGLU tiles: reuse the packing the previous call made from the same W
 };
 static int env_gemm_dbg() { return getenv("DF_GEMM_DBG") ? atoi(getenv("DF_GEMM_DBG")) : 0; }
+
+// launch_gemm; its refusal (made on the host, nothing launched) names the rule
+static void test_launch_gemm(const GemmParams& g, int tile, int batch, hipStream_t s, const char* role = "") {
+  const char* why = nullptr;
+  const hipError_t e = launch_gemm(g, tile, batch, s, &why);
+  if (e == hipErrorInvalidValue)
+    fail("%slaunch_gemm refused tile %d / split-K %d / batch %d (%dx%dx%d): %s (%s)", role, tile, g.splitk, batch, g.M, g.N, g.K,
+         hipGetErrorString(e), why ? why : "the launch itself");
+  HIPCHK(e);
+}
 
 // descriptor -> GemmParams -> launch: everything the eight single-GEMM entry points below do on the device
 static void run_test_gemm(const df_test_gemm_desc& d, const TestGemmOpts& o, hipStream_t s) {
@@ -158,7 +176,7 @@ static void run_test_gemm(const df_test_gemm_desc& d, const TestGemmOpts& o, hip
     fail("df_test_gemm (%dx%dx%d, Cin %d): the contraction length must be a multiple of 64", g.M, g.N, g.K, g.Cin);
   if (d.defer_reduce && g.splitk < 2) fail("df_test_gemm: defer_reduce needs split-K");
   g.dbg = o.dbg;
-  if (o.require_valid && !gemm_tile_valid(g, d.tile, batch, g.splitk)) fail("tile %d / split-K %d refused this problem", d.tile, g.splitk);
+  if (o.tuner_policy && !gemm_split_worth_tuning(g, d.tile, g.splitk)) fail("tile %d / split-K %d refused this problem", d.tile, g.splitk);
   const size_t slab_bytes = (size_t)g.splitk * g.M * g.N * 4 * (g.taps == 4 ? 4 : 1);     // phase-decomposed: four slabs per split
   if (g.splitk > 1) g.partial = test_partial(slab_bytes);
   else if (g.dbg & 64) g.partial = test_partial((size_t)4096 * 32 * 8);      // per-block clock stamps (df_test_scratch_read)
@@ -166,11 +184,7 @@ static void run_test_gemm(const df_test_gemm_desc& d, const TestGemmOpts& o, hip
     if (g.N % 320 != 0 || !g.ln_cs || !g.bias) fail("tile %d: N = %d is not a multiple of 320, or no column sums / bias", d.tile, g.N);
     test_pack_w320(g, o.keep_w320, s);
   }
-  const hipError_t e = launch_gemm(g, d.tile, batch, s);
-  if (e == hipErrorInvalidValue)
-    fail("launch_gemm refused tile %d / split-K %d / batch %d (%dx%dx%d): %s", d.tile, g.splitk, batch, g.M, g.N, g.K,
-         hipGetErrorString(e));
-  HIPCHK(e);
+  test_launch_gemm(g, d.tile, batch, s);
   if (d.defer_reduce && d.slabs_out) HIPCHK(hipMemcpyAsync(d.slabs_out, g.partial, slab_bytes, hipMemcpyDeviceToDevice, s));
 }
 
@@ -196,7 +210,7 @@ static df_test_gemm_desc test_desc_conv(const void* A, const void* W, void* C, i
   return d;
 }
 
-// ungated, DF_GEMM_DBG from the environment: the tools time (tile, split-K) pairs the tuner would not pick
+// outside the tuner's split policy too, DF_GEMM_DBG from the environment: the tools time (tile, split-K) pairs the tuner would not pick
 int df_test_gemm(const uint16_t* A, const uint16_t* W, float* C, int M, int N, int K, int tile, int splitk, void* stream) {
   return guard([&] {
     df_test_gemm_desc d = test_desc(A, W, C, tile, splitk);
@@ -230,7 +244,7 @@ int df_test_gemm_dual(const uint16_t* A, const uint16_t* A2, const uint16_t* W, 
   });
 }
 
-// ungated like df_test_gemm (a halo tile's refusal of a map is launch_gemm's own), DF_GEMM_DBG from the environment
+// as df_test_gemm: no split policy, DF_GEMM_DBG from the environment
 int df_test_conv3x3(const uint16_t* A, const uint16_t* W, const float* bias, float* C, int NB, int H, int Wd, int Cin,
                     int Cout, int stride, int ups, int tile, int splitk, void* stream) {
   return guard([&] {
@@ -289,21 +303,18 @@ int df_test_xattn_chain(const uint16_t* ctx, const uint16_t* Wkv, const float* W
     const float scale = 1.0f / sqrtf((float)(C / heads));
     if (Tc < 1 || Tc > 32 || C % 64 != 0 || C % heads != 0 || (C / heads) % 8 != 0 || HT % 64 != 0 || T % 64 != 0 || Dc % 64 != 0)
       fail("xattn chain: C %d / heads %d / Tc %d / T %d / Dc %d outside what the folded form takes", C, heads, Tc, T, Dc);
-    auto run = [&](const GemmParams& g, int tile, int batch, const char* what) {
-      if (!gemm_tile_valid(g, tile, batch, 1)) fail("xattn chain: tile %d refused %s", tile, what);
-      HIPCHK(launch_gemm(g, tile, batch, s));
-    };
+    auto run = [&](const GemmParams& g, int tile, int batch, const char* what) { test_launch_gemm(g, tile, batch, s, what); };
     {
       GemmParams g = Builder::gp_linear(ctx, NB * Tc, Dc, Wkv, 2 * C);
       Builder::out_b16(g, kv, 2 * C);
-      run(g, TILE_64x64, 1, "ctx.kv");
+      run(g, TILE_64x64, 1, "xattn chain ctx.kv: ");
     }
     HIPCHK(launch_xattn_expand(kv, Kexp, Vexp, NB, Tc, 32, C, heads, s));
     HIPCHK(launch_pack_lnq_t(Wq, gamma, WqT, C, scale, s));
     {
       GemmParams g = Builder::gp_linear(Kexp, NB * HT, C, WqT, C);
       Builder::out_b16(g, G, C);
-      run(g, TILE_64x64, 1, "ctx.g");
+      run(g, TILE_64x64, 1, "xattn chain ctx.g: ");
     }
     HIPCHK(launch_xattn_rowstats(G, Kexp, bq, scale, C, (long)NB * HT, cs, bb, s));
     {
@@ -311,7 +322,7 @@ int df_test_xattn_chain(const uint16_t* ctx, const uint16_t* Wkv, const float* W
       g.w_bs = (long)HT * C;
       Builder::out_b16(g, Vo, HT);
       g.c_bs = (long)C * HT;
-      run(g, TILE_64x64, NB, "ctx.vo");
+      run(g, TILE_64x64, NB, "xattn chain ctx.vo: ");
     }
     {
       GemmParams g = Builder::gp_linear(xb, M, C, G, HT);
@@ -320,7 +331,7 @@ int df_test_xattn_chain(const uint16_t* ctx, const uint16_t* Wkv, const float* W
       g.ln_stats = (const float2*)xstats; g.ln_slots = C / 64; g.ln_C = C; g.ln_eps = 1e-5f; g.ln_cs = cs;
       g.bias = bb;
       g.sm_w = 32; g.sm_valid = Tc;
-      run(g, tile_xs, 1, "st.xs");
+      run(g, tile_xs, 1, "xattn chain st.xs: ");
     }
     {
       GemmParams g = Builder::gp_linear(P, M, HT, Vo, C);
@@ -328,7 +339,7 @@ int df_test_xattn_chain(const uint16_t* ctx, const uint16_t* Wkv, const float* W
       Builder::out_f32(g, out, C);
       g.bias = bo;
       g.res = x; g.ldr = C;
-      run(g, tile_xo, 1, "st.xo");
+      run(g, tile_xo, 1, "xattn chain st.xo: ");
     }
   });
 }
@@ -368,8 +379,7 @@ int df_test_ln_chain(const uint16_t* A0, const uint16_t* W0, const float* b0, co
       g.stats = st; g.stats_slots = slots;
       g.splitk = sk0;
       if (sk0 > 1) g.partial = test_partial((size_t)sk0 * M * C * 4);
-      if (!gemm_tile_valid(g, tile0, 1, sk0)) fail("producer: tile %d / split-K %d not valid here", tile0, sk0);
-      HIPCHK(launch_gemm(g, tile0, 1, s));
+      test_launch_gemm(g, tile0, 1, s, "producer: ");
     }
     {
       GemmParams g = Builder::gp_linear(xb, M, C, w1p, N1);
@@ -383,8 +393,7 @@ int df_test_ln_chain(const uint16_t* A0, const uint16_t* W0, const float* b0, co
       }
       g.splitk = sk1;
       if (sk1 > 1) g.partial = test_partial((size_t)sk1 * M * N1 * 4);
-      if (!gemm_tile_valid(g, tile1, 1, sk1)) fail("consumer: tile %d / split-K %d not valid here", tile1, sk1);
-      HIPCHK(launch_gemm(g, tile1, 1, s));
+      test_launch_gemm(g, tile1, 1, s, "consumer: ");
     }
     HIPCHK(hipStreamSynchronize(s));
     for (void* p : {(void*)xb, (void*)st, (void*)w1p, (void*)cs, (void*)bb}) (void)hipFree(p);
@@ -575,8 +584,7 @@ int df_test_conv3x3_bwd_data(const uint16_t* dY, const float* W_oihw, uint16_t* 
     }
     g.splitk = splitk;
     if (splitk > 1) g.partial = test_partial((size_t)splitk * g.M * g.N * 4);
-    if (!gemm_tile_valid(g, tile, 1, splitk)) fail("tile %d / split-K %d refused this problem", tile, splitk);
-    HIPCHK(launch_gemm(g, tile, 1, (hipStream_t)stream));
+    test_launch_gemm(g, tile, 1, (hipStream_t)stream);
   });
 }
 

@@ -148,7 +148,12 @@ void autotune_plan(df_ctx* c, Plan* pl, hipStream_t s) {
         q.splitk = sk;
         q.partial = pl->partial;
         // res may alias C: results are garbage during tuning but are recomputed by the next real run
-        if (launch_gemm(q, t, o.batch, s) != hipSuccess) continue;
+        // gemm_tile_valid said yes with launch_gemm's own rules: a failure here is an error, not a candidate to skip
+        const char* why = nullptr;
+        const hipError_t le = launch_gemm(q, t, o.batch, s, &why);
+        if (le != hipSuccess)
+          fail("autotune: %s (GEMM %dx%dx%d) on tile %d / split-K %d failed after gemm_tile_valid accepted it: %s (%s)", o.tag, g.M, g.N, g.K,
+               t, sk, hipGetErrorString(le), why ? why : "the launch itself");
         HIPCHK(hipEventRecord(e0, s));
         for (int r = 0; r < 3; ++r) (void)launch_gemm(q, t, o.batch, s);
         HIPCHK(hipEventRecord(e1, s));

@@ -342,7 +342,6 @@ __device__ __forceinline__ void geglu_persistent_body(const GemmParams& p) {
 
 template <int BM, int WGM, int WGN, int NST, int LNS, bool DBG>
 hipError_t launch_pgeglu(const GemmParams& p, hipStream_t stream) {
-  if (p.ln_slots > LNS || (long)p.M * p.ldc * 2 >= ((long)1 << 31)) return hipErrorInvalidValue;
   constexpr size_t lds = (size_t)NST * (BM + 128) * BK * 2 + (size_t)2 * BM * 8;
   static_assert(2 * lds <= 160 * 1024, "two resident blocks per CU");
   static bool attr_set = false;
@@ -359,14 +358,6 @@ hipError_t launch_pgeglu(const GemmParams& p, hipStream_t stream) {
 }
 
 }  // namespace
-
-bool pgeglu_valid(const GemmParams& p, int tile, int batch, int splitk) {
-  if ((tile == TILE_PGEGLU_128 || tile == TILE_PGEGLU_128_W8) && p.ln_slots > 10) return false;     // their row-statistics registers hold 10 slots (C <= 640)
-  return p.geglu && p.ln_stats && p.ln_cs && p.bias && splitk <= 1 && batch <= 1 && p.taps == 1 && p.out_bf16 && !p.res &&
-         !p.rowbias && !p.aux && !p.stats && !p.vt && p.w_rows == 0 && p.Cin2 == 0 && p.dup_rows == 0 && p.sm_w == 0 &&
-         !p.relu && !p.silu && !p.store_nchw && p.alpha == 1.f && (p.N % 128) == 0 && (p.K % 64) == 0 && p.K >= 128 &&
-         p.ln_slots <= 20 && p.C != nullptr;
-}
 
 hipError_t launch_gemm_pgeglu(int tile_cfg, const GemmParams& p, hipStream_t stream) {
 #define DF_TILE_PGEGLU0(T, M0, M1, M2, M3, BM, BN, WGM, WGN, NST, PS, LNS)                                                    \

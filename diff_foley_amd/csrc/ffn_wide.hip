@@ -338,13 +338,6 @@ hipError_t launch_pack_w320(const uint16_t* w, const float* cs, const float* bb,
   return hipGetLastError();
 }
 
-bool wgeglu_valid(const GemmParams& p, int tile, int batch, int splitk) {
-  return p.geglu && p.ln_stats && p.W_w320 && p.cs_w320 && p.bias_w320 && splitk <= 1 && batch <= 1 && p.taps == 1 && p.out_bf16 && !p.res &&
-         !p.rowbias && !p.aux && !p.stats && !p.vt && p.w_rows == 0 && p.Cin2 == 0 && p.dup_rows == 0 && p.sm_w == 0 && !p.relu && !p.silu &&
-         !p.store_nchw && p.alpha == 1.f && (p.N % 320) == 0 && (p.K % 64) == 0 && p.K >= 128 && p.ln_slots <= 20 && (p.ln_slots % 5) == 0 &&
-         p.C != nullptr && (p.ldc % 8) == 0 && (p.lda % 8) == 0;
-}
-
 hipError_t launch_gemm_wgeglu(int tile_cfg, const GemmParams& p, hipStream_t stream) {
 #define DF_TILE_WGEGLU0(T, M0, M1, M2, M3, BM, BN, WGM, WGN, NST, PS, LNS)                                                           \
   static_assert((BN) == 320 && (BM) % 64 == 0 && (WGM) == 4 && (WGN) == 2 && (M0) && !(M1) && !(M2) && !(M3), "the wide GEGLU kernel"); \

@@ -133,10 +133,44 @@ static inline void gemm_tile_dims(int cfg, int* bm, int* bn) {
   *bn = kGemmTiles[cfg].bn;
 }
 
-// Can (tile, batch, splitk) run this problem?  (halo tiles: 3x3 stride-1 convs whose patch geometry fits LDS)
+// Epilogue specialisations.  A kernel carries ONLY the epilogue it runs: the per-launch fixed cost on this chip grows by
+// ~1-2 us between a 5 KB and a 45 KB code object (cold instruction fetch at every kernel boundary; tools/icache_probe.py),
+// which is 10-20 % of the small GEMMs of the transformer blocks.
+//   LEAN   fp32 | operand-type row-major out, bias, per-sample / per-position bias, residual   (the UNet's common case)
+//   SPLITK partial slab store (the reduce kernel applies the epilogue)
+//   GEGLU  value * gelu(gate) on (32 | 32) column groups, optionally LayerNorm-folded
+//   PROD   LEAN + per-row partial statistics + operand-type copy (producers of a LayerNorm-folded consumer)
+//   LNC    LayerNorm-folded consumer, optionally with the transposed V^T column range (fused QKV)
+//   ANY    everything else: alpha, ReLU, aux copy, NCHW store, unaligned shapes (scalar fallback)
+//   XS     cross-attention scores: LayerNorm-folded, softmax over each 32-column head, operand-type out
+enum { EPI_LEAN = 0, EPI_SPLITK = 1, EPI_GEGLU = 2, EPI_PROD = 3, EPI_LNC = 4, EPI_ANY = 5, EPI_XS = 6 };
+
+// The vectorised epilogues (in-kernel and split-K reduce alike) move 4 consecutive columns of C, the residual, the row bias and the
+// operand copy as one 16-byte (8-byte) access: row-major output, every row stride a multiple of 4 elements.
+static inline bool gemm_rows_vec4(const GemmParams& p) {
+  return !p.store_nchw && (p.ldc & 3) == 0 && (p.ldr & 3) == 0 && (p.ld_rowbias & 3) == 0 && (p.ld_aux & 3) == 0;
+}
+// Only the in-kernel epilogues run batched: they step C and the residual by blockIdx.z * c_bs / res_bs, so those strides have to keep
+// the alignment too.  The reduce kernels never see a batch (split-K and batch exclude each other) and do not ask this.
+static inline bool gemm_batch_vec4(const GemmParams& p) { return (p.res_bs & 3) == 0 && (p.c_bs & 3) == 0; }
+
+// How one (problem, tile, batch, split-K) is launched: gemm_route decides, launch_gemm only dispatches on it.
+enum GemmReduce { DF_RED_NONE = 0, DF_RED_VEC, DF_RED_SCALAR, DF_RED_CFG, DF_RED_DEFERRED };      // who sums split-K slabs (MODE 3: of the x2 map)
+struct GemmRoute {
+  int family, mode, epi, zdim, reduce;         // GemmTileFamily, MODE 0 .. 3, EPI_*, grid z (split-K or batch), GemmReduce
+  int th, tw, halo_ring_bytes;                 // halo tiles: the block's patch of output pixels, bytes of its LDS operand ring
+  size_t lds;                                  // halo tiles: dynamic LDS of the launch
+};
+// nullptr: the tile can run this problem at this batch and split-K, *out (may be null) says how; else the rule that refuses.
+// Every correctness rule of the GEMM stack is here, once; pure host arithmetic, no HIP call.
+const char* gemm_route(const GemmParams& p, int tile, int batch, int splitk, GemmRoute* out);
+// POLICY, not correctness: the splits of a K loop the tuner bothers to time (every slab keeps at least two K steps; halo tiles: one
+// 64-channel chunk).  A finer split runs and is right, it is just never the fastest.
+bool gemm_split_worth_tuning(const GemmParams& p, int tile, int splitk);
+// What the plan builder and the tuner ask: gemm_route says yes, and the split is inside the tuner's policy.
 bool gemm_tile_valid(const GemmParams& p, int tile, int batch, int splitk);
 
-// batch > 1 and splitk > 1 are mutually exclusive.
-hipError_t launch_gemm(const GemmParams& p, int tile_cfg, int batch, hipStream_t stream);
+// Calls gemm_route with p.splitk first: a refusal is hipErrorInvalidValue, *why (when given) the rule; nothing is launched.
+hipError_t launch_gemm(const GemmParams& p, int tile_cfg, int batch, hipStream_t stream, const char** why = nullptr);
 // (32 x | 32 gate) GEGLU packing (rows of K operand values, column sums, folded bias) -> the wide tiles' 320-column packing (ffn_wide.hip)
 hipError_t launch_pack_w320(const uint16_t* w, const float* cs, const float* bb, uint16_t* wo, float* cso, float* bbo, int N, int K, hipStream_t s);

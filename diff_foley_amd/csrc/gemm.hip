@@ -11,6 +11,7 @@
 // lane*16), so the swizzle is applied to the per-lane SOURCE chunk instead (rule: both sides or neither).
 // Out-of-range rows / conv padding use an out-of-bounds buffer offset: the hardware then writes zeros.
 #include <algorithm>
+#include <numeric>
 #include <stdlib.h>
 
 #include "gemm_impl.h"
@@ -20,14 +21,12 @@ hipError_t launch_gemm_m0a(int tile_cfg, int epi, const GemmParams& p, int zdim,
 hipError_t launch_gemm_m0b(int tile_cfg, int epi, const GemmParams& p, int zdim, hipStream_t stream);
 hipError_t launch_gemm_m1(int tile_cfg, int epi, const GemmParams& p, int zdim, hipStream_t stream);
 hipError_t launch_gemm_m2(int tile_cfg, int epi, const GemmParams& p, int zdim, hipStream_t stream);
-hipError_t launch_gemm_halo(int tile_cfg, int epi, const GemmParams& p, int zdim, hipStream_t stream);
+hipError_t launch_gemm_halo(int tile_cfg, int epi, const GemmParams& p, int zdim, size_t lds, hipStream_t stream);
 hipError_t launch_gemm_m3(int tile_cfg, int epi, const GemmParams& p, int zdim, hipStream_t stream);
 hipError_t launch_gemm_ps(int mode, int tile_cfg, int epi, const GemmParams& p, int zdim, hipStream_t stream);
 hipError_t launch_gemm_ps_small(int mode, int tile_cfg, int epi, const GemmParams& p, int zdim, hipStream_t stream);
 hipError_t launch_gemm_pgeglu(int tile_cfg, const GemmParams& p, hipStream_t stream);
-bool pgeglu_valid(const GemmParams& p, int tile, int batch, int splitk);
 hipError_t launch_gemm_wgeglu(int tile_cfg, const GemmParams& p, hipStream_t stream);
-bool wgeglu_valid(const GemmParams& p, int tile, int batch, int splitk);
 
 namespace {
 
@@ -156,151 +155,206 @@ __global__ __launch_bounds__(256) void splitk_reduce_vec_kernel(GemmParams p) {
 #endif
 }
 
-}  // namespace
-
-bool gemm_tile_valid(const GemmParams& p, int tile, int batch, int splitk) {
-  const int nk = p.K / 64;
-  if (p.taps == 4) {     // phase-decomposed upsample conv (MODE 3): a subset of the generic tiles, plain epilogues only
-    if (!gemm_tile_has_mode(tile, 3) || batch > 1) return false;
-    if (p.geglu || p.vt || p.ln_stats || p.stats || p.w_rows > 0 || p.sm_w > 0 || p.Cin2 > 0 || p.res || p.store_nchw) return false;
-    if (splitk > 1 && (p.N & 3) != 0) return false;
-    return splitk == 1 || nk / splitk >= 2;
+// split counts the vectorised reduce is built for (the tuner's list); any other count takes the scalar reduce
+#define DF_REDUCE_SPLITS(X) X(2) X(3) X(4) X(6) X(8) X(12) X(16) X(24) X(32)
+bool reduce_vec_built(int sk) {
+#define DF_RED(SK) case SK:
+  switch (sk) {
+    DF_REDUCE_SPLITS(DF_RED) return true;
+    default: return false;
   }
-  if (gemm_tile_is_pgeglu(tile)) return pgeglu_valid(p, tile, batch, splitk);
-  if (gemm_tile_is_wgeglu(tile)) return wgeglu_valid(p, tile, batch, splitk);
-  if (!gemm_tile_has_mode(tile, gemm_mode(p))) return false;     // no such instantiation (gemm_tiles.def M0 .. M3), or no such tile
-  if (!gemm_tile_is_halo(tile)) {
-    if (tile < 0 || tile >= TILE_ALL) return false;
-    if (p.geglu && ((p.N & 63) != 0 || (p.ldc & 3) != 0)) return false;   // GEGLU needs the vectorised block epilogue
-    int bm_, bn_;
-    gemm_tile_dims(tile, &bm_, &bn_);
-    if (p.vt && (splitk > 1 || batch > 1 || p.vt_col0 % bn_ != 0)) return false;   // transposed-V tiles are whole tiles
-    if (p.ln_stats && (batch > 1 || (p.geglu && splitk > 1))) return false;
-    if (p.ln_stats && p.ln_slots > gemm_ln_max_slots()) return false;    // thread r folds the partials of tile row r (<= 20 slots)
-    if (p.stats && batch > 1) return false;
-    if (p.w_rows > 0 && (batch > 1 || p.taps != 1 || p.w_rows % bm_ != 0 || p.M % p.w_rows != 0)) return false;
-    if (p.sm_w > 0 && (p.sm_w != 32 || splitk > 1 || !p.ln_stats || !p.out_bf16 || p.w_rows <= 0 || (p.N & 31) != 0 || p.geglu ||
-                       p.vt || p.res || p.rowbias || p.aux || p.alpha != 1.f || !p.bias))
-      return false;
-    if (p.dup_rows > 0 && (batch > 1 || p.geglu || p.vt || p.sm_w > 0 || p.store_nchw || (p.N & 3) != 0 || (p.ldc & 3) != 0 ||
-                           (p.ldr & 3) != 0 || (p.ld_rowbias & 3) != 0 || (p.ld_aux & 3) != 0))
-      return false;
-    if (p.Cin2 > 0 && (batch > 1 || (p.Cin2 & 63) != 0 || !p.A2)) return false;
-    if (p.Cin2 > 0 && p.taps == 9 && (p.stride != 1 || p.ups)) return false;    // conv: the folded 1x1 skip connection
-    if (p.Cin2 > 0 && p.taps != 9 && (p.taps != 1 || p.Cin2 >= p.K)) return false;   // linear: K columns [K-Cin2, K) from A2
-    if (splitk > 1 && (p.N & 3) != 0) return false;          // partial slabs are written and reduced as float4
-    return splitk == 1 || (batch <= 1 && nk / splitk >= 2);
-  }
-  if (splitk > 1 && (p.N & 3) != 0) return false;
-  if (p.dup_rows > 0 && (p.store_nchw || (p.N & 3) != 0 || (p.ldc & 3) != 0 || (p.ldr & 3) != 0 || (p.ld_rowbias & 3) != 0 || (p.ld_aux & 3) != 0))
-    return false;
-  // the folded skip connection: generic stride-1 kernel, and (round 5) a one-tap K tail of the producer-specialised halo tiles
-  const bool halo_ps = tile >= TILE_HALO_PS_192x64 && tile <= TILE_HALO_PS_128x128;
-  if (p.Cin2 > 0 && (!halo_ps || (p.Cin2 & 63) != 0 || !p.A2 || (p.lda2 & 7) != 0)) return false;
-  if (p.taps != 9 || p.stride != 1 || p.ups != 0 || p.geglu || batch > 1) return false;
-  int bm, bn, th, tw;
-  gemm_tile_dims(tile, &bm, &bn);
-  if (!halo_patch(p.H, p.Wd, bm, &th, &tw)) return false;
-  const int threads = gemm_halo_dma_threads(tile), rpp = threads / 8;
-  const int hr = (bm / (th * tw)) * (th + 2) * (tw + 2);
-  const int apass = (hr + rpp - 1) / rpp, wpass = (bn + rpp - 1) / rpp;
-  if (apass > 12) return false;
-  if (p.Cin2 > 0 && 3 * bm > 2 * apass * rpp) return false;      // the tail's three activation slots live in the two halo buffers
-  const int nstw = gemm_halo_ring(tile);   // weight ring depth (4; 8 for the weight-streaming variants)
-  if (((size_t)2 * apass * rpp + (size_t)nstw * wpass * rpp) * 128 + (size_t)std::max(bm, hr) * 4 > 160 * 1024) return false;
-  if ((p.lda & 7) != 0) return false;           // the halo-row table keeps a 3-bit key in the low bits of a pixel's byte offset
-  const int nchunk = p.Cin / 64;
-  return splitk == 1 || nchunk / splitk >= 1;
+#undef DF_RED
 }
 
-hipError_t launch_gemm(const GemmParams& p, int tile_cfg, int batch, hipStream_t stream) {
-  if (gemm_tile_is_pgeglu(tile_cfg)) {
-    if (!pgeglu_valid(p, tile_cfg, batch, p.splitk)) return hipErrorInvalidValue;
-    return launch_gemm_pgeglu(tile_cfg, p, stream);
-  }
-  if (gemm_tile_is_wgeglu(tile_cfg)) {
-    if (!wgeglu_valid(p, tile_cfg, batch, p.splitk)) return hipErrorInvalidValue;
-    return launch_gemm_wgeglu(tile_cfg, p, stream);
-  }
-  const int zdim = (p.splitk > 1) ? p.splitk : (batch > 0 ? batch : 1);
-  if (p.ln_stats || p.stats || p.vt) {     // these epilogues exist in the vectorised paths only
-    const bool vec = !p.store_nchw && (p.N & 63) == 0 && (p.ldc & 3) == 0 && (p.ldr & 3) == 0 && (p.ld_rowbias & 3) == 0 &&
-                     (p.ld_aux & 3) == 0;
-    if (!vec || (p.vt && ((p.M & 3) != 0 || (p.vt_T & 3) != 0 || (p.ldvt & 3) != 0 || p.taps != 1))) return hipErrorInvalidValue;
-    if (p.ln_stats && p.taps != 1) return hipErrorInvalidValue;
-  }
-  // epilogue specialisation (gemm_impl.h): the kernel carries only the code it runs
-  const bool vec = !p.store_nchw && (p.N & 3) == 0 && (p.ldc & 3) == 0 && (p.ldr & 3) == 0 && (p.ld_rowbias & 3) == 0 &&
-                   (p.res_bs & 3) == 0 && (p.c_bs & 3) == 0 && (p.ld_aux & 3) == 0;
-  int epi;
-  if (p.splitk > 1) epi = EPI_SPLITK;
-  else if (p.sm_w > 0) epi = EPI_XS;
-  else if (p.geglu) epi = EPI_GEGLU;
-  else if (p.ln_stats || p.vt) epi = EPI_LNC;
-  else if (p.stats) epi = EPI_PROD;
-  else if (!vec || p.relu || p.aux || p.alpha != 1.f) epi = EPI_ANY;
-  else epi = EPI_LEAN;
-  if ((epi == EPI_GEGLU || epi == EPI_LNC || epi == EPI_PROD) && (p.taps != 1 || p.alpha != 1.f || p.relu || p.silu || !vec))
-    return hipErrorInvalidValue;
-  if (epi == EPI_LNC && (!p.ln_stats || p.aux)) return hipErrorInvalidValue;
-  if (epi == EPI_XS && (!p.ln_stats || p.taps != 1 || !vec || (p.N & 63) != 0)) return hipErrorInvalidValue;
-  hipError_t e;
-  const int mode = gemm_mode(p), part = (tile_cfg >= 0 && tile_cfg < TILE_ALL) ? kGemmTiles[tile_cfg].part : 0;
-  if (mode == 3) {
-    if (batch > 1 || gemm_tile_is_halo(tile_cfg) || p.OH != p.H || p.OW != p.Wd || p.K != 4 * p.Cin || p.w_bs != (long)p.N * p.K)
-      return hipErrorInvalidValue;
-    e = launch_gemm_m3(tile_cfg, epi, p, zdim, stream);
-  } else if (gemm_tile_is_halo(tile_cfg)) e = launch_gemm_halo(tile_cfg, epi, p, zdim, stream);
-  else if (gemm_tile_is_ps(tile_cfg)) e = part ? launch_gemm_ps_small(mode, tile_cfg, epi, p, zdim, stream) : launch_gemm_ps(mode, tile_cfg, epi, p, zdim, stream);
-  else if (mode == 0) e = part ? launch_gemm_m0b(tile_cfg, epi, p, zdim, stream) : launch_gemm_m0a(tile_cfg, epi, p, zdim, stream);
-  else if (mode == 1) e = launch_gemm_m1(tile_cfg, epi, p, zdim, stream);
-  else e = launch_gemm_m2(tile_cfg, epi, p, zdim, stream);
-  if (e != hipSuccess) return e;
-  if (p.splitk > 1 && !p.defer_reduce && mode == 3) {
-    GemmParams q = p;
-    q.M = 4 * p.M;           // the slabs hold the x2 output map
-    q.taps = 1;
-    const long total = (long)q.M * (q.N >> 2);
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 4096) blocks = 4096;
-    if ((q.N & 3) != 0 || (q.ldc & 3) != 0 || q.store_nchw) return hipErrorInvalidValue;
-#define DF_RED3(SK) case SK: hipLaunchKernelGGL(splitk_reduce_vec_kernel<SK>, dim3(blocks), dim3(256), 0, stream, q); break;
-    switch (p.splitk) {
-      DF_RED3(2) DF_RED3(3) DF_RED3(4) DF_RED3(6) DF_RED3(8) DF_RED3(12) DF_RED3(16) DF_RED3(24) DF_RED3(32)
-      default: hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, stream, q); break;
-    }
-#undef DF_RED3
-    return hipGetLastError();
-  }
-  if (p.splitk > 1 && p.dup_rows > 0 && p.defer_reduce) return hipErrorInvalidValue;
-  if (p.splitk > 1 && !p.defer_reduce) {
-    const bool vec = !p.geglu && !p.store_nchw && (p.N & 3) == 0 && (p.ldc & 3) == 0 && (p.ldr & 3) == 0 &&
-                     (p.ld_rowbias & 3) == 0 && (p.ld_aux & 3) == 0;
-    if (vec) {
-      const long total = (long)p.M * (p.N >> 2);
-      int blocks = (int)((total + 255) / 256);
-      if (blocks > 4096) blocks = 4096;
-#define DF_RED(SK) case SK: hipLaunchKernelGGL(splitk_reduce_vec_kernel<SK>, dim3(blocks), dim3(256), 0, stream, p); break;
-      switch (p.splitk) {
-        DF_RED(2) DF_RED(3) DF_RED(4) DF_RED(6) DF_RED(8) DF_RED(12) DF_RED(16) DF_RED(24) DF_RED(32)
-        default: hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, stream, p); break;
-      }
+// q: the GEMM's parameters (MODE 3: with the x2 map's row count, as one-tap rows)
+hipError_t launch_splitk_reduce(const GemmParams& q, int reduce, hipStream_t stream) {
+  const bool vec = reduce == DF_RED_VEC, cfg = reduce == DF_RED_CFG;
+  const long total = vec ? (long)q.M * (q.N >> 2) : cfg ? (long)(q.M >> 1) * q.N : (long)q.M * (q.geglu ? q.N >> 1 : q.N);     // threads
+  const int blocks = (int)std::min<long>((total + 255) / 256, vec ? 4096 : 2048);
+#define DF_RED(SK) case SK: hipLaunchKernelGGL(splitk_reduce_vec_kernel<SK>, dim3(blocks), dim3(256), 0, stream, q); break;
+  if (vec) switch (q.splitk) { DF_REDUCE_SPLITS(DF_RED) }
+  else if (cfg) hipLaunchKernelGGL(splitk_reduce_cfg_kernel, dim3(blocks), dim3(256), 0, stream, q);
+  else hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, stream, q);
 #undef DF_RED
+  return hipGetLastError();
+}
+
+// Spatial patch (th x tw output pixels) owned by one block of a halo kernel with BM rows.
+bool halo_patch(int H, int W, int BM, int* th, int* tw) {
+  const int w = (W % 16 == 0) ? 16 : W;
+  if (w <= 0 || H <= 0 || BM % w != 0) return false;
+  *th = std::gcd(H, BM / w);     // tallest patch that tiles both the image and the block (192 rows: 3 x 4x16)
+  *tw = w;
+  return true;
+}
+
+// The persistent and the wide GEGLU projection (ffn.hip, ffn_wide.hip): one LayerNorm-folded form each, nothing else.
+const char* route_fused_geglu(const GemmParams& p, const GemmTileInfo& t, int batch, int sk) {
+  if (!p.geglu || !p.ln_stats) return "the fused GEGLU tiles run the LayerNorm-folded GEGLU projection only";
+  if (sk > 1 || batch > 1) return "the fused GEGLU tiles take neither split-K nor a batch";
+  if (!p.out_bf16 || !p.C || p.res || p.rowbias || p.aux || p.stats || p.vt || p.w_rows != 0 || p.Cin2 != 0 || p.dup_rows != 0 ||
+      p.sm_w != 0 || p.relu || p.silu || p.store_nchw || p.alpha != 1.f)
+    return "the fused GEGLU tiles store operand-type value * gelu(gate) and know no other epilogue feature";
+  if ((p.K % 64) != 0 || p.K < 128) return "the fused GEGLU tiles need K >= 128 in whole 64-element steps";
+  if (p.ln_slots > gemm_ln_max_slots()) return "more than 20 LayerNorm statistics slots";
+  if (t.family == DF_FAM_PGEGLU) {
+    if (!p.ln_cs || !p.bias) return "the persistent GEGLU kernel needs column sums and the folded bias";
+    if ((p.N % 128) != 0) return "the persistent GEGLU kernel needs N % 128 == 0";
+    if (p.ln_slots > t.lns) return "more LayerNorm statistics slots than this tile's registers hold (LNS)";
+    if ((long)p.M * p.ldc * 2 >= ((long)1 << 31)) return "the persistent GEGLU kernel's output exceeds 2 GiB of buffer addressing";
+  } else {
+    if (!p.W_w320 || !p.cs_w320 || !p.bias_w320) return "the wide GEGLU tiles need the 320-column packing";
+    if ((p.N % 320) != 0 || (p.ln_slots % 5) != 0) return "the wide GEGLU tiles need N % 320 == 0 and ln_slots % 5 == 0";
+    if ((p.ldc % 8) != 0 || (p.lda % 8) != 0) return "the wide GEGLU tiles need lda and ldc in whole 16-byte chunks";
+  }
+  return nullptr;
+}
+
+// Halo tiles: the block's patch, its LDS staging (gemm_impl.h conv3x3_halo_kernel) and what must fit
+const char* route_halo(const GemmParams& p, int tile, GemmRoute& r) {
+  const GemmTileInfo& t = kGemmTiles[tile];
+  if (p.geglu) return "halo tiles: no geglu";
+  if (!halo_patch(p.H, p.Wd, t.bm, &r.th, &r.tw)) return "halo tile: no patch of this block tiles the map";
+  const int rpp = gemm_halo_dma_threads(tile) / 8;             // 128-B LDS rows one DMA pass fills
+  const int pb = t.bm / (r.th * r.tw), hr = pb * (r.th + 2) * (r.tw + 2);
+  const int apass = (hr + rpp - 1) / rpp, wpass = (t.bn + rpp - 1) / rpp;
+  if (apass > 12) return "halo tile: the halo takes more than 12 DMA passes";
+  // the folded skip connection is a one-tap K tail of the producer-specialised halo tiles; its three activation slots live in the
+  // two halo buffers
+  if (p.Cin2 > 0 && !t.ps) return "halo tile: only the producer-specialised ones take the folded skip";
+  if (p.Cin2 > 0 && 3 * t.bm > 2 * apass * rpp) return "halo tile: the folded skip's three slots do not fit the two halo buffers";
+  if (p.Cin2 > 0 && (p.lda2 & 7) != 0) return "halo tile: lda2 % 8 != 0";
+  const size_t ring = ((size_t)2 * apass * rpp + (size_t)t.ring * wpass * rpp) * 128;
+  r.halo_ring_bytes = (int)ring;
+  r.lds = ring + (size_t)std::max(t.bm, hr) * 4;          // + the prologue's halo-row table / the epilogue's row table
+  if (r.lds > 160 * 1024) return "halo tile: the staged patch exceeds 160 KiB of LDS";
+  if ((p.lda & 7) != 0) return "halo tile: lda % 8 != 0 (the halo-row table keeps a 3-bit key in the low bits of a byte offset)";
+  if ((long)p.M / (r.th * r.tw) + pb > (1 << 22)) return "halo tile: 2^22 patches or more (FastDiv range)";      // patches, rounded up to whole blocks
+  return nullptr;
+}
+
+}  // namespace
+
+const char* gemm_route(const GemmParams& p, int tile, int batch, int splitk, GemmRoute* out) {
+  GemmRoute r{};
+  const int sk = splitk > 1 ? splitk : 1;
+  if (tile < 0 || tile >= TILE_ALL) return "no such tile";
+  const GemmTileInfo& t = kGemmTiles[tile];
+  r.family = t.family;
+  r.mode = gemm_mode(p);
+  r.zdim = sk > 1 ? sk : (batch > 0 ? batch : 1);
+  // which (tile, MODE) pairs are built: gemm_tiles.def M0 .. M3 (a retired id: none)
+  if (!((t.modes >> r.mode) & 1)) return "this tile is not built for the problem's MODE";
+  if (t.family == DF_FAM_PGEGLU || t.family == DF_FAM_WGEGLU) {
+    if (const char* no = route_fused_geglu(p, t, batch, sk)) return no;
+    r.epi = EPI_GEGLU;
+    if (out) *out = r;
+    return nullptr;
+  }
+  const bool rows4 = gemm_rows_vec4(p) && (p.N & 3) == 0;      // what every vectorised epilogue and the vectorised reduce need
+  if (sk > 1 && batch > 1) return "split-K and a batch exclude each other";
+  if (sk > 1 && (p.N & 3) != 0) return "split-K with N % 4 != 0 (the slabs are written and reduced as float4)";
+  // epilogue features and the forms they exist in
+  const bool lnf = p.ln_stats || p.stats || p.vt;
+  if (lnf && (!rows4 || (p.N & 63) != 0))
+    return "ln_stats / stats / vt exist in the vectorised epilogues only: row-major, N % 64 == 0, leading dimensions % 4 == 0";
+  if (lnf && batch > 1) return "ln_stats / stats / vt with a batch";
+  if (p.ln_stats && r.mode != 0) return "ln_stats on a conv";
+  if (p.ln_stats && p.ln_slots > gemm_ln_max_slots()) return "more than 20 LayerNorm statistics slots";
+  if (p.geglu && ((p.N & 63) != 0 || (p.ldc & 3) != 0)) return "geglu needs the vectorised block epilogue: N % 64 == 0, ldc % 4 == 0";
+  if (p.vt && (sk > 1 || p.vt_col0 % t.bn != 0)) return "vt: transposed-V tiles are whole tiles (no split-K, vt_col0 % BN == 0)";
+  if (p.vt && ((p.M & 3) != 0 || (p.vt_T & 3) != 0 || (p.ldvt & 3) != 0 || r.mode != 0 || !p.ln_stats))
+    return "vt: LayerNorm-folded linear GEMM with M, vt_T and ldvt % 4 == 0";
+  if (p.w_rows > 0 && (batch > 1 || r.mode != 0 || p.w_rows % t.bm != 0 || p.M % p.w_rows != 0))
+    return "w_rows: linear, unbatched, w_rows % BM == 0 and M % w_rows == 0";
+  if (p.sm_w > 0 && (p.sm_w != 32 || sk > 1 || !p.ln_stats || !p.out_bf16 || p.w_rows <= 0 || (p.N & 31) != 0 || p.geglu || p.vt || p.res ||
+                     p.rowbias || p.aux || p.alpha != 1.f || !p.bias))
+    return "sm_w: the score epilogue is 32 columns a head, LayerNorm-folded, per-sample weights, bias, operand-type out, no split-K";
+  if (p.dup_rows > 0 && (batch > 1 || p.geglu || p.vt || p.sm_w > 0 || !rows4))
+    return "dup_rows: plain row-major vectorised epilogues only, no geglu / vt / sm_w, no batch";
+  if (p.Cin2 > 0 && (batch > 1 || (p.Cin2 & 63) != 0 || !p.A2)) return "Cin2: unbatched, whole 64-channel steps from A2";
+  if (p.Cin2 > 0 && r.mode != 1 && (r.mode != 0 || p.Cin2 >= p.K))
+    return "Cin2: a stride-1 conv's folded 1x1 skip, or the K columns [K - Cin2, K) of a linear GEMM";
+  if (r.mode == 3) {     // phase-decomposed upsample conv: plain epilogues on the x2 map
+    if (batch > 1 || p.geglu || p.stats || p.res || p.store_nchw) return "MODE 3: plain unbatched row-major epilogues without residual only";
+    if (p.OH != p.H || p.OW != p.Wd || p.K != 4 * p.Cin || p.w_bs != (long)p.N * p.K)
+      return "MODE 3: OH x OW is the input map, K = 4 Cin, w_bs = N K between the four phases' weights";
+  }
+  if (t.family == DF_FAM_HALO) {
+    if (batch > 1) return "halo tiles with a batch";
+    if (const char* no = route_halo(p, tile, r)) return no;
+  }
+  // the epilogue the kernel carries (gemm_impl.h): only the code it runs
+  const bool vec = rows4 && gemm_batch_vec4(p);
+  if (sk > 1) r.epi = EPI_SPLITK;
+  else if (p.sm_w > 0) r.epi = EPI_XS;
+  else if (p.geglu) r.epi = EPI_GEGLU;
+  else if (p.ln_stats || p.vt) r.epi = EPI_LNC;
+  else if (p.stats) r.epi = EPI_PROD;
+  else if (!vec || p.relu || p.aux || p.alpha != 1.f) r.epi = EPI_ANY;
+  else r.epi = EPI_LEAN;
+  // which (MODE, epilogue) pairs are built (gemm_m0a .. gemm_ps2.hip, gemm_halo.hip): LEAN, SPLITK and ANY for every MODE,
+  // the rest for MODE 0 alone
+  if (r.epi == EPI_GEGLU || r.epi == EPI_PROD || r.epi == EPI_LNC || r.epi == EPI_XS) {
+    if (r.mode != 0) return "the GEGLU / PROD / LNC / XS epilogues are built for MODE 0 (linear) only";
+    if (!vec) return "the GEGLU / PROD / LNC / XS epilogues are vectorised: N, leading dimensions and batch strides % 4 == 0";
+    if (r.epi != EPI_XS && (p.alpha != 1.f || p.relu || p.silu)) return "alpha / relu / silu with a GEGLU / PROD / LNC epilogue";
+    if (r.epi == EPI_LNC && p.aux) return "aux with ln_stats";
+  }
+  if (sk > 1) {     // who sums the slabs
+    const bool vec_red = !p.geglu && rows4 && reduce_vec_built(sk);
+    if (!vec_red && (p.ln_stats || p.stats || p.dup_rows > 0 || p.no_c_store))
+      return "ln_stats / stats / dup_rows / no_c_store with a split-K only the scalar reduce sums (geglu, or a split count the vectorised one is not built for)";
+    if (p.defer_reduce) {
+      if (p.dup_rows > 0) return "dup_rows with a deferred split-K reduce";
+      r.reduce = DF_RED_DEFERRED;
+    } else if (r.mode == 3 && !rows4) {
+      return "MODE 3 split-K: the reduce of the x2 map needs aligned rows (leading dimensions % 4 == 0)";
+    } else if (vec_red) {
+      r.reduce = DF_RED_VEC;
     } else if (p.cfg_out) {
       if (!p.store_nchw || p.geglu || p.res || p.aux || p.silu || p.relu || (p.M & 1) || p.hw_out <= 0 || (p.M >> 1) % p.hw_out != 0)
-        return hipErrorInvalidValue;
-      const long total = (long)(p.M >> 1) * p.N;
-      int blocks = (int)((total + 255) / 256);
-      if (blocks > 2048) blocks = 2048;
-      hipLaunchKernelGGL(splitk_reduce_cfg_kernel, dim3(blocks), dim3(256), 0, stream, p);
+        return "cfg_out: NCHW store of an even batch of whole samples, bias only";
+      r.reduce = DF_RED_CFG;
     } else {
-      const int nout = p.geglu ? (p.N >> 1) : p.N;
-      const long total = (long)p.M * nout;
-      int blocks = (int)((total + 255) / 256);
-      if (blocks > 2048) blocks = 2048;
-      hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, stream, p);
+      r.reduce = DF_RED_SCALAR;
     }
-    e = hipGetLastError();
   }
-  return e;
+  if (out) *out = r;
+  return nullptr;
+}
+
+bool gemm_split_worth_tuning(const GemmParams& p, int tile, int splitk) {
+  if (splitk <= 1) return true;
+  return gemm_tile_is_halo(tile) ? p.Cin / 64 / splitk >= 1 : p.K / 64 / splitk >= 2;
+}
+
+bool gemm_tile_valid(const GemmParams& p, int tile, int batch, int splitk) {
+  return gemm_route(p, tile, batch, splitk, nullptr) == nullptr && gemm_split_worth_tuning(p, tile, splitk);
+}
+
+hipError_t launch_gemm(const GemmParams& p, int tile_cfg, int batch, hipStream_t stream, const char** why) {
+  GemmRoute r;
+  const char* no = gemm_route(p, tile_cfg, batch, p.splitk, &r);
+  if (why) *why = no;
+  if (no) return hipErrorInvalidValue;
+  const int part = kGemmTiles[tile_cfg].part;
+  hipError_t e;
+  if (r.family == DF_FAM_PGEGLU) return launch_gemm_pgeglu(tile_cfg, p, stream);
+  if (r.family == DF_FAM_WGEGLU) return launch_gemm_wgeglu(tile_cfg, p, stream);
+  if (r.family == DF_FAM_HALO) {
+    GemmParams q = p;
+    q.th = r.th; q.tw = r.tw; q.halo_ring_bytes = r.halo_ring_bytes;
+    e = launch_gemm_halo(tile_cfg, r.epi, q, r.zdim, r.lds, stream);
+  } else if (r.family == DF_FAM_PS) e = part ? launch_gemm_ps_small(r.mode, tile_cfg, r.epi, p, r.zdim, stream) : launch_gemm_ps(r.mode, tile_cfg, r.epi, p, r.zdim, stream);
+  else if (r.mode == 0) e = part ? launch_gemm_m0b(tile_cfg, r.epi, p, r.zdim, stream) : launch_gemm_m0a(tile_cfg, r.epi, p, r.zdim, stream);
+  else if (r.mode == 1) e = launch_gemm_m1(tile_cfg, r.epi, p, r.zdim, stream);
+  else if (r.mode == 2) e = launch_gemm_m2(tile_cfg, r.epi, p, r.zdim, stream);
+  else e = launch_gemm_m3(tile_cfg, r.epi, p, r.zdim, stream);
+  if (e != hipSuccess || r.reduce == DF_RED_NONE || r.reduce == DF_RED_DEFERRED) return e;
+  if (r.mode != 3) return launch_splitk_reduce(p, r.reduce, stream);
+  GemmParams q = p;
+  q.M = 4 * p.M;           // the slabs hold the x2 output map
+  q.taps = 1;
+  return launch_splitk_reduce(q, r.reduce, stream);
 }

@@ -20,30 +20,6 @@ namespace {
 
 constexpr int BK = 64;
 
-// Epilogue specialisations.  A kernel carries ONLY the epilogue it runs: the per-launch fixed cost on this chip grows by
-// ~1-2 us between a 5 KB and a 45 KB code object (cold instruction fetch at every kernel boundary; tools/icache_probe.py),
-// which is 10-20 % of the small GEMMs of the transformer blocks.
-//   LEAN   fp32 | operand-type row-major out, bias, per-sample / per-position bias, residual   (the UNet's common case)
-//   SPLITK partial slab store (the reduce kernel applies the epilogue)
-//   GEGLU  value * gelu(gate) on (32 | 32) column groups, optionally LayerNorm-folded
-//   PROD   LEAN + per-row partial statistics + operand-type copy (producers of a LayerNorm-folded consumer)
-//   LNC    LayerNorm-folded consumer, optionally with the transposed V^T column range (fused QKV)
-//   ANY    everything else: alpha, ReLU, aux copy, NCHW store, unaligned shapes (scalar fallback)
-enum { EPI_LEAN = 0, EPI_SPLITK = 1, EPI_GEGLU = 2, EPI_PROD = 3, EPI_LNC = 4, EPI_ANY = 5, EPI_XS = 6 };
-
-// Spatial patch (th x tw output pixels) owned by one block of a halo kernel with BM rows.
-bool halo_patch(int H, int W, int BM, int* th, int* tw) {
-  const int w = (W % 16 == 0) ? 16 : W;
-  if (w <= 0 || BM % w != 0) return false;
-  int h = BM / w;
-  if (h > H) h = H;
-  while (h > 1 && (H % h != 0 || BM % (h * w) != 0)) --h;     // tallest patch that tiles both the image and the block (192 rows: 3 x 4x16)
-  if (h <= 0 || H % h != 0 || BM % (h * w) != 0) return false;
-  *th = h;
-  *tw = w;
-  return true;
-}
-
 // Sum over the 16 lanes of a DPP row (lanes 16k .. 16k+15), result in every lane: two quad butterflies and two row
 // rotations, all DPP modifiers on VALU adds -- no LDS-pipe traffic (ds_bpermute) in the epilogue.
 __device__ __forceinline__ float row16_sum(float v) {
@@ -1289,7 +1265,7 @@ __device__ __forceinline__ void conv3x3_halo_body(const GemmParams& p) {
   // LDS cycles, SQ_LDS_BANK_CONFLICT).  The halo slot is swizzled by the pixel's x-pair plus SC * (image row counter):
   // conflict-free for TW = 16 (SC = 0) and TW = 8 (SC = 4) at every tap shift.
   const int SC = (TW == 16) ? 0 : 4;
-  // all quotients below are of values < 2^22 (launch_halo checks the patch count): FastDiv instead of 32-bit division
+  // all quotients below are of values < 2^22 (gemm_route checks the patch count): FastDiv instead of 32-bit division
   const FastDiv fd_hwp(HWp), fd_tw2(TW + 2), fd_pimg(npy * npx), fd_npx(npx), fd_ppx(PPX), fd_tw(TW);
   constexpr int MAXAP = 12;
   // Halo row -> source pixel, ONE decomposition per halo row of the block (round 4): every thread of the block (both roles)
@@ -1680,18 +1656,17 @@ __device__ __forceinline__ void conv3x3_halo_body(const GemmParams& p) {
 #endif
 }
 
+// The launch templates only launch: whether (p, tile, split-K) may run, and how, is gemm_route's (gemm.hip).
 template <int BM, int BN, int WGM, int WGN, int NST, int MODE, int EPI, int NSTB = NST, int PS = 0>
 hipError_t launch_cfg(const GemmParams& p, int zdim, hipStream_t stream) {
   const int nbm = (p.M + BM - 1) / BM, nbn = (p.N + BN - 1) / BN;
   constexpr size_t ring = ((size_t)BM * NST + (size_t)BN * NSTB) * BK * 2;     // operand rings (A: NST slots, W: NSTB slots)
   constexpr size_t stage = (size_t)BM * (BN + 4) * 4 + (size_t)BM * 8 + (MODE == 3 ? (size_t)BM * 4 : 0);   // epilogue tile + (mean, rstd) row table (+ MODE 3 pixel table)
-  const size_t base = ring > stage ? ring : stage;
-  const size_t lds = base;
-  if (p.ln_stats && p.ln_slots > 20) return hipErrorInvalidValue;     // LNS of the kernel
-  if (lds > 160 * 1024) return hipErrorInvalidValue;
+  constexpr size_t lds = ring > stage ? ring : stage;
+  static_assert(lds <= 160 * 1024, "a row of gemm_tiles.def whose rings or epilogue tile exceed the CU's LDS");
   static bool attr_set = false;
   if (!attr_set) {
-    const size_t cap = std::min<size_t>(160 * 1024, base + (size_t)5 * 64 * WGM * WGN * 8);
+    const size_t cap = std::min<size_t>(160 * 1024, lds + (size_t)5 * 64 * WGM * WGN * 8);
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_kernel<BM, BN, WGM, WGN, NST, MODE, EPI, NSTB, PS>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)cap);
     if (e != hipSuccess) return e;
@@ -1702,24 +1677,9 @@ hipError_t launch_cfg(const GemmParams& p, int zdim, hipStream_t stream) {
   return hipGetLastError();
 }
 
-
+// p.th / p.tw / p.halo_ring_bytes and lds come from the route
 template <int BM, int BN, int WGM, int WGN, int NSTW, int EPI, int PS = 0>
-hipError_t launch_halo(const GemmParams& pin, int zdim, hipStream_t stream) {
-  constexpr int NT = 64 * WGM * WGN * (1 + PS), RPP = (PS ? 64 * WGM * WGN * PS : NT) / 8;
-  GemmParams p = pin;
-  if (!halo_patch(p.H, p.Wd, BM, &p.th, &p.tw)) return hipErrorInvalidValue;
-  const int ppx = p.th * p.tw;
-  if (ppx <= 0 || BM % ppx != 0 || p.H % p.th != 0 || p.Wd % p.tw != 0 || p.stride != 1 || p.ups != 0 || p.taps != 9)
-    return hipErrorInvalidValue;
-  const int PB = BM / ppx, HR = PB * (p.th + 2) * (p.tw + 2);
-  const int APASS = (HR + RPP - 1) / RPP;
-  if (APASS > 12) return hipErrorInvalidValue;
-  if (p.Cin2 > 0 && (PS == 0 || 3 * BM > 2 * APASS * RPP || (p.Cin2 % BK) != 0 || !p.A2)) return hipErrorInvalidValue;   // folded-skip tail
-  constexpr int WPASS = (BN + RPP - 1) / RPP;
-  const size_t ring = ((size_t)2 * APASS * RPP + (size_t)NSTW * WPASS * RPP) * BK * 2;
-  const size_t lds = ring + (size_t)std::max(BM, HR) * 4;          // + the prologue's halo-row table / the epilogue's row table
-  p.halo_ring_bytes = (int)ring;
-  if (lds > 160 * 1024) return hipErrorInvalidValue;
+hipError_t launch_halo(const GemmParams& p, int zdim, size_t lds, hipStream_t stream) {
   static size_t attr = 0;
   if (lds > attr) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_halo_kernel<BM, BN, WGM, WGN, NSTW, EPI, PS>),
@@ -1727,10 +1687,10 @@ hipError_t launch_halo(const GemmParams& pin, int zdim, hipStream_t stream) {
     if (e != hipSuccess) return e;
     attr = lds;
   }
-  const int npatch = p.M / ppx;
-  const int nbm = (npatch + PB - 1) / PB, nbn = (p.N + BN - 1) / BN;
-  if ((long)nbm * PB >= (1 << 22)) return hipErrorInvalidValue;      // FastDiv range of the patch decomposition
-  hipLaunchKernelGGL((conv3x3_halo_kernel<BM, BN, WGM, WGN, NSTW, EPI, PS>), dim3(nbm * nbn, 1, zdim), dim3(NT), lds, stream, p);
+  const int ppx = p.th * p.tw, PB = BM / ppx;
+  const int nbm = (p.M / ppx + PB - 1) / PB, nbn = (p.N + BN - 1) / BN;
+  hipLaunchKernelGGL((conv3x3_halo_kernel<BM, BN, WGM, WGN, NSTW, EPI, PS>), dim3(nbm * nbn, 1, zdim), dim3(64 * WGM * WGN * (1 + PS)), lds,
+                     stream, p);
   return hipGetLastError();
 }
 

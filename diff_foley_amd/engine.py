@@ -189,6 +189,7 @@ _SIGS = {
     "df_test_conv3x3_bwd_data": [C.c_void_p] * 5 + [C.c_int] * 8 + [C.c_void_p],
     "df_test_gemm_ex": [C.POINTER(GemmDesc), C.c_void_p],
     "df_test_gemm_valid": [C.POINTER(GemmDesc), C.c_int, C.c_int, C.c_int],
+    "df_test_gemm_why": [C.POINTER(GemmDesc), C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int],
     "df_test_gemm_key": [C.POINTER(GemmDesc), C.c_int, C.c_char_p, C.c_int],
     "df_test_gemm_tile_info": [C.c_int, C.POINTER(GemmTile)],
     "df_test_xattn_chain": [C.c_void_p] * 10 + [C.c_int] * 6 + [C.c_void_p] * 10 + [C.c_int, C.c_int, C.c_void_p],

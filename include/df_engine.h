@@ -258,9 +258,10 @@ int df_debug_saturation_label(df_ctx* ctx, int64_t index, char* buf, int64_t len
 int df_test_scratch_read(void* host, int64_t bytes);     /* the shared scratch of the test entry points (debug stamps) */
 /* df_test_gemm, _gemm_epi, _gemm_dual, df_test_conv3x3, _conv3x3_skip, _conv3x3_ups4 and df_test_geglu are fixed-shape fills of
  * the df_test_gemm_desc below, run through the one path of df_test_gemm_ex: K (convs: Cin too) must be a multiple of 64, and a refusal
- * of the launch reads "launch_gemm refused ...: invalid argument".  _gemm_epi, _gemm_dual, _conv3x3_skip, _conv3x3_ups4 and
- * df_test_geglu ask gemm_tile_valid first ("tile T / split-K S refused this problem"); df_test_gemm and df_test_conv3x3 do not, like
- * df_test_gemm_ex -- they also take GemmParams::dbg from the environment (DF_GEMM_DBG; bit 6: per-block clock stamps).
+ * of the launch reads "launch_gemm refused ...: invalid argument (the rule that refuses)": launch_gemm itself refuses whatever cannot
+ * run (csrc/gemm.h gemm_route), on the host, before anything is launched.  _gemm_epi, _gemm_dual, _conv3x3_skip, _conv3x3_ups4 and
+ * df_test_geglu also apply the tuner's split policy ("tile T / split-K S refused this problem"); df_test_gemm and df_test_conv3x3 do
+ * not, like df_test_gemm_ex -- they also take GemmParams::dbg from the environment (DF_GEMM_DBG; bit 6: per-block clock stamps).
  * df_test_geglu: the LayerNorm-folded GEGLU projection (stats [M][K/64] float2, cs / bias [N1], out operand type [M][N1/2]); dbg goes
  * to GemmParams::dbg except bit 7, which keeps the wide tiles' 320-column packing made from the same W by the previous call. */
 int df_test_geglu(const uint16_t* A_dev, const uint16_t* W_dev, const void* stats_dev, const float* cs_dev, const float* bias_dev,
@@ -416,8 +417,13 @@ typedef struct df_test_gemm_desc {
   void* vt; int vt_col0, vt_T, ldvt;
 } df_test_gemm_desc;
 int df_test_gemm_ex(const df_test_gemm_desc* d, void* stream);
-/* gemm_tile_valid(d, tile, batch, splitk): 1 / 0, or -1 (message in df_last_error) for a malformed descriptor.  Host only. */
+/* gemm_tile_valid(d, tile, batch, splitk): 1 / 0, or -1 (message in df_last_error) for a malformed descriptor.  Host only.
+ * 1 exactly when df_test_gemm_why returns 0. */
 int df_test_gemm_valid(const df_test_gemm_desc* d, int tile, int batch, int splitk);
+/* Why: 0 = launch_gemm runs it and the tuner would try it; 1 = it runs, but the split is outside the tuner's policy (too few K steps
+ * per slab to be worth timing); 2 = launch_gemm refuses it, the rule NUL-terminated (truncated) into buf[n] (buf may be null);
+ * -1 = malformed descriptor (message in df_last_error).  Host only. */
+int df_test_gemm_why(const df_test_gemm_desc* d, int tile, int batch, int splitk, char* buf, int n);
 /* The tune-cache key of the descriptor's GEMM (csrc/engine_tune.hip tune_key: M_N_K_taps_stride_ups_batch_geglu_eEPI; the deferred-reduce
  * bit from d->defer_reduce), NUL-terminated into buf[n].  Returns 0, or -1 (message in df_last_error).  Host only. */
 int df_test_gemm_key(const df_test_gemm_desc* d, int batch, char* buf, int n);
