@@ -7,7 +7,8 @@ this package is the Python host side mirroring the reference's interface.
 from . import synth  # noqa: F401
 from . import schedule  # noqa: F401
 from . import engine  # noqa: F401
-from .ldm import LatentDiffusion, AlignmentClassifier, CAVPInference, instantiate_from_config  # noqa: F401
+from .ldm import (LatentDiffusion, AlignmentClassifier, CAVPInference, DiagonalGaussianDistribution,  # noqa: F401
+                  instantiate_from_config)
 from .samplers import DDIMSampler, PLMSSampler, DPMSolverSampler  # noqa: F401
 from .video import ExtractCAVPFeatures, frames_to_tensor  # noqa: F401
 from .vocoder import inverse_op, mel_to_wave  # noqa: F401
@@ -28,7 +29,7 @@ def stage2_config(unet=None, vae=None, cond=None):
         first_stage_config=dict(target="diff_foley.models.autoencoder.AutoencoderKL",
                                 params=dict(embed_dim=vae["embed_dim"], monitor="val/rec_loss",
                                             ddconfig=dict(double_z=True, z_channels=vae["z_channels"], resolution=256,
-                                                          in_channels=3, out_ch=vae["out_ch"], ch=vae["ch"],
+                                                          in_channels=vae.get("in_channels", 3), out_ch=vae["out_ch"], ch=vae["ch"],
                                                           ch_mult=list(vae["ch_mult"]),
                                                           num_res_blocks=vae["num_res_blocks"], attn_resolutions=[],
                                                           dropout=0.0),

@@ -987,6 +987,162 @@ hipError_t launch_conv3x3_fewout(const uint16_t* X, const uint16_t* Wt, const fl
   return hipGetLastError();
 }
 
+namespace {
+// 3x3 convolution (stride 1, zero padding 1) from a HANDFUL of input channels -- the mirror of conv3x3_fewout: the VAE encoder's conv_in
+// (stage1_autoencoder/model.py:479-483, 3 -> 128 channels over the full 128 x 512 mel image).  Input NCHW fp32, output the fp32 NHWC
+// residual stream [NB*H*W][ldo].  On the implicit-GEMM route the 3 input channels would be packed to a 64-channel operand (an 8 MB per
+// sample round trip) and the K loop would run 9 * 64 = 576 deep for 27 useful products (21x the MFMA work); the op is bound by writing
+// the output once (H * W * Cout * 4 bytes per sample, 33.5 MB at the Stage-2 shape).  fp32 VALU arithmetic: K = 9 * Cin <= 36 is too
+// short for the matrix cores to matter, and neither the image nor the weights are rounded to the operand type.
+// A block owns a FI_TH-row x FI_TW-pixel patch.  Its (FI_TH + 2) x (FI_TW + 2) halo is staged in LDS per input plane from row-contiguous
+// reads of the NCHW planes (zeros outside the image).  Cout / 4 neighbouring lanes form a SLOT: lane `cg` of a slot owns output channels
+// [4 cg, 4 cg + 4) and holds their 4 x 9 Cin weights in registers for the whole block (read once, straight from the OIHW tensor: 36 Cin
+// contiguous floats per lane).  A slot computes a RUN of four horizontally neighbouring pixels at a time: per (ci, ky) six staged values
+// (one 16-B + one 8-B LDS read, the same address in every lane of the slot = a broadcast) feed 3 taps x 4 pixels x 4 channels FMAs, summed in
+// (ci, ky, kx) order.  Every lane stores 16 B per pixel; a pixel's Cout floats are contiguous, so one wavefront store instruction covers
+// 256 / Cout whole pixels (1 KiB, write-through like the GEMM epilogues).
+constexpr int FI_TH = 4, FI_TW = 32;
+[[maybe_unused]] constexpr int FI_PITCH = FI_TW + 4;      // LDS row pitch in floats: 16-B aligned runs, columns [0, FI_TW + 2) used
+template <int CIN>
+__global__ __launch_bounds__(256) void conv3x3_fewin_kernel(const float* __restrict__ X /*[NB][CIN][H][W]*/, const float* __restrict__ Wt /*[Cout][CIN][3][3]*/,
+                                                            const float* __restrict__ bias, float* __restrict__ out /*[NB*H*W][ldo]*/, int ldo,
+                                                            int H, int W, int Cout) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  __shared__ __attribute__((aligned(16))) float sX[CIN * (FI_TH + 2) * FI_PITCH];
+  const int tid = threadIdx.x;
+  const int tpr = (W + FI_TW - 1) / FI_TW, tpc = (H + FI_TH - 1) / FI_TH;
+  const int bx = blockIdx.x % tpr, by = (blockIdx.x / tpr) % tpc, n = blockIdx.x / (tpr * tpc);
+  const int x0 = bx * FI_TW, y0 = by * FI_TH;
+  // ---- stage the halo patch: consecutive threads read consecutive pixels of one plane row
+  for (int i = tid; i < CIN * (FI_TH + 2) * (FI_TW + 2); i += 256) {
+    const int px = i % (FI_TW + 2), r = i / (FI_TW + 2);            // r = ci * (FI_TH + 2) + py
+    const int py = r % (FI_TH + 2), ci = r / (FI_TH + 2);
+    const int yy = y0 + py - 1, xx = x0 + px - 1;
+    float v = 0.f;
+    if (yy >= 0 && yy < H && xx >= 0 && xx < W) v = X[(((long)n * CIN + ci) * H + yy) * W + xx];
+    sX[r * FI_PITCH + px] = v;
+  }
+  // ---- this lane's weights and bias: output channels [4 cg, 4 cg + 4)
+  const int lpp = Cout >> 2, cg = tid % lpp, slot = tid / lpp, nslots = 256 / lpp;
+  float w[4][9 * CIN];
+  {
+    const float4* wp = reinterpret_cast<const float4*>(Wt + (long)cg * 4 * 9 * CIN);      // 36 CIN floats: 16-B aligned
+    float flat[4 * 9 * CIN];
+#pragma unroll
+    for (int i = 0; i < 9 * CIN; ++i) {
+      const float4 t = wp[i];
+      flat[4 * i] = t.x; flat[4 * i + 1] = t.y; flat[4 * i + 2] = t.z; flat[4 * i + 3] = t.w;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int k = 0; k < 9 * CIN; ++k) w[j][k] = flat[j * 9 * CIN + k];
+  }
+  float4 b4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (bias) b4 = *reinterpret_cast<const float4*>(bias + 4 * cg);
+  __syncthreads();
+  constexpr int RUNS = FI_TH * FI_TW / 4;
+#pragma unroll 1
+  for (int r = slot; r < RUNS; r += nslots) {
+    const int ry = r / (FI_TW / 4), rx = (r % (FI_TW / 4)) * 4;        // patch coordinates of the run's first pixel
+    const int y = y0 + ry, x = x0 + rx;
+    if (y >= H || x >= W) continue;
+    float acc[4][4];
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[p][j] = 0.f;
+#pragma unroll
+    for (int ci = 0; ci < CIN; ++ci)
+#pragma unroll
+      for (int ky = 0; ky < 3; ++ky) {
+        const float* row = sX + (ci * (FI_TH + 2) + ry + ky) * FI_PITCH + rx;      // staged columns rx .. rx + 5 = image x - 1 .. x + 4
+        const float4 lo = *reinterpret_cast<const float4*>(row);
+        const float2 hi = *reinterpret_cast<const float2*>(row + 4);
+        const float v[6] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y};
+#pragma unroll
+        for (int kx = 0; kx < 3; ++kx)
+#pragma unroll
+          for (int p = 0; p < 4; ++p)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[p][j] = fmaf(v[p + kx], w[j][(ci * 3 + ky) * 3 + kx], acc[p][j]);
+      }
+    float* o = out + (((long)n * H + y) * W + x) * ldo + 4 * cg;
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+      if (x + p < W)
+        st_wt(reinterpret_cast<float4*>(o + (long)p * ldo),
+              make_float4(acc[p][0] + b4.x, acc[p][1] + b4.y, acc[p][2] + b4.z, acc[p][3] + b4.w));
+  }
+#endif
+}
+
+// out[b][o][hw] = bq[o] + sum_i Wq[o][i] * h[(b * HW + hw) * ld + i]: one thread per output element, fp32 (i ascending)
+__global__ __launch_bounds__(256) void conv1x1_rows_nchw_kernel(const float* __restrict__ h, int ld, const float* __restrict__ Wq,
+                                                                const float* __restrict__ bq, float* __restrict__ out, long total,
+                                                                int HW, int Cin, int Cout) {
+  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
+    const int hw = (int)(e % HW), o = (int)((e / HW) % Cout);
+    const long b = e / ((long)HW * Cout);
+    const float* row = h + (b * HW + hw) * ld;
+    const float* wr = Wq + (long)o * Cin;
+    float acc = 0.f;
+    for (int i = 0; i < Cin; ++i) acc = fmaf(wr[i], row[i], acc);
+    out[e] = acc + (bq ? bq[o] : 0.f);
+  }
+}
+
+// DiagonalGaussianDistribution.sample() (stage1_autoencoder/model.py:38-47) times `scale`: the clamp comes before the exp, as there.
+// expf is the device library's full-range single-precision exponential (1 ulp, HIP math API), not the fast __expf.
+__global__ __launch_bounds__(256) void posterior_sample_kernel(const float* __restrict__ moments, const float* __restrict__ noise,
+                                                               float* __restrict__ z, long total, long chw, float scale) {
+  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
+    const long b = e / chw, r = e - b * chw;
+    const float mean = moments[b * 2 * chw + r];
+    float v = mean;
+    if (noise) {
+      const float lv = fminf(fmaxf(moments[b * 2 * chw + chw + r], -30.0f), 20.0f);
+      v = mean + expf(0.5f * lv) * noise[e];
+    }
+    z[e] = scale * v;
+  }
+}
+}  // namespace
+
+bool conv3x3_fewin_ok(int H, int W, int Cin, int Cout, int ldo) {
+  return Cin >= 1 && Cin <= 4 && (Cout == 64 || Cout == 128 || Cout == 256) && ldo >= Cout && (ldo & 3) == 0 && H > 0 && W > 0;
+}
+
+hipError_t launch_conv3x3_fewin(const float* X, const float* Wt, const float* bias, float* out, int ldo, int NB, int H, int W, int Cin,
+                                int Cout, hipStream_t s) {
+  if (!conv3x3_fewin_ok(H, W, Cin, Cout, ldo) || NB <= 0) return hipErrorInvalidValue;
+  const long blocks = (long)NB * ((H + FI_TH - 1) / FI_TH) * ((W + FI_TW - 1) / FI_TW);
+  if (blocks > 0x7fffffffL) return hipErrorInvalidValue;
+  const dim3 g((unsigned)blocks), b(256);
+  switch (Cin) {
+    case 1: hipLaunchKernelGGL(conv3x3_fewin_kernel<1>, g, b, 0, s, X, Wt, bias, out, ldo, H, W, Cout); break;
+    case 2: hipLaunchKernelGGL(conv3x3_fewin_kernel<2>, g, b, 0, s, X, Wt, bias, out, ldo, H, W, Cout); break;
+    case 3: hipLaunchKernelGGL(conv3x3_fewin_kernel<3>, g, b, 0, s, X, Wt, bias, out, ldo, H, W, Cout); break;
+    default: hipLaunchKernelGGL(conv3x3_fewin_kernel<4>, g, b, 0, s, X, Wt, bias, out, ldo, H, W, Cout); break;
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_conv1x1_rows_nchw(const float* h, int ld, const float* Wq, const float* bq, float* out, int B, int HW, int Cin,
+                                    int Cout, hipStream_t s) {
+  if (B <= 0 || HW <= 0 || Cin <= 0 || Cin > 128 || Cout <= 0 || Cout > 128 || ld < Cin) return hipErrorInvalidValue;
+  const long total = (long)B * Cout * HW;
+  hipLaunchKernelGGL(conv1x1_rows_nchw_kernel, dim3(grid_for(total)), dim3(256), 0, s, h, ld, Wq, bq, out, total, HW, Cin, Cout);
+  return hipGetLastError();
+}
+
+hipError_t launch_posterior_sample(const float* moments, const float* noise, float* z, int B, int zc, long HW, float scale, hipStream_t s) {
+  if (B <= 0 || zc <= 0 || HW <= 0) return hipErrorInvalidValue;
+  const long chw = (long)zc * HW, total = (long)B * chw;
+  hipLaunchKernelGGL(posterior_sample_kernel, dim3(grid_for(total)), dim3(256), 0, s, moments, noise, z, total, chw, scale);
+  return hipGetLastError();
+}
+
 hipError_t launch_pack_conv_weight(const float* w, uint16_t* out, int O, int I, int KH, int KW, int Ipad,
                                    hipStream_t s) {
   const long n = (long)O * KH * KW * Ipad;

@@ -101,6 +101,12 @@ void df_destroy(df_ctx* ctx) {
 
 int df_config_unet(df_ctx* c, const df_unet_config* cfg) { return guard([&] { c->ucfg = *cfg; c->has_unet = true; }); }
 int df_config_vae(df_ctx* c, const df_vae_config* cfg) { return guard([&] { c->vcfg = *cfg; c->has_vae = true; }); }
+int df_config_vae_encoder(df_ctx* c, const df_vae_encoder_config* cfg) {
+  return guard([&] {
+    c->has_vae_enc = cfg != nullptr;
+    c->ecfg = cfg ? *cfg : df_vae_encoder_config{};
+  });
+}
 int df_config_cond(df_ctx* c, const df_cond_config* cfg) { return guard([&] { c->kcfg = *cfg; c->has_cond = true; }); }
 int df_config_cavp(df_ctx* c, const df_cavp_config* cfg) { return guard([&] { c->pcfg = *cfg; c->has_cavp = true; }); }
 int df_config_classifier(df_ctx* c, const df_unet_config* cfg) { return guard([&] { c->ccfg = *cfg; c->has_cls = true; }); }
@@ -137,6 +143,10 @@ int df_finalize(df_ctx* c) {
     HIPCHK(hipSetDevice(c->device));
     if (c->has_unet) build_emb_table(c, 0);
     if (c->has_cls) build_emb_table(c, 1);
+    if (c->has_vae_enc) {      // the encoder is configured only by a caller that loads its tensors: every one of them has to be there
+      if (!c->has_vae) fail("vae encoder configured without df_config_vae (it shares the decoder's ch / ch_mult / z_channels)");
+      for (auto& n : vae_encoder_tensor_names(c)) (void)c->rt(n);
+    }
     HIPCHK(hipDeviceSynchronize());
     c->plans.clear();
     if (c->reloaded) {     // every packed operand copy (casts, GEGLU / LN-folded / BN-folded / stacked packings) is rebuilt
@@ -366,6 +376,34 @@ int df_vae_decode(df_ctx* c, const float* z, float* out, int B, int H, int W, vo
   });
 }
 
+// The encoder's widest operand is the full-resolution map x ch channels (2 ch at half resolution is half of that); the bound below is
+// the decoder's (2 ch at full resolution), so both directions slice a batch the same way.
+static int vae_encode_chunk(df_ctx* c, int H, int W) {
+  const size_t per_sample = (size_t)H * W * (size_t)c->vcfg.ch * 2 * 2;
+  const int chunk = (int)std::max<size_t>(1, (((size_t)1 << 31) - 1) / std::max<size_t>(per_sample, 1));
+  return std::min(chunk, 16);
+}
+
+int df_vae_encode(df_ctx* c, const float* x, float* moments, int B, int H, int W, void* stream) {
+  return guard([&] {
+    if (!c->has_vae || !c->has_vae_enc) fail("vae encoder not configured (df_config_vae_encoder, with the encoder's tensors loaded)");
+    need_positive("vae encode", {{"batch", B}, {"H", H}, {"W", W}});
+    const int f = 1 << (c->vcfg.n_mult - 1);
+    // torch's padded stride-2 convs floor an odd map; this engine sizes every level as H / 2 and refuses what does not divide
+    if (H % f || W % f) fail("vae encode: image %dx%d is not a multiple of the encoder's downsampling (%d)", H, W, f);
+    const int chunk = vae_encode_chunk(c, H, W);
+    const int cin = c->ecfg.in_channels, mc = 2 * c->vcfg.embed_dim;
+    for (int b0 = 0; b0 < B; b0 += chunk) {
+      const int nb = std::min(chunk, B - b0);
+      Plan* p = get_plan(c, keyf("vaeenc_%d_%d_%d", nb, H, W), [&](Plan* pl) { build_vae_encoder(c, pl, nb, H, W); });
+      RunArgs a;
+      a.x = x + (size_t)b0 * cin * H * W;
+      a.out = moments + (size_t)b0 * mc * (H / f) * (W / f);
+      run_ops(c, p, 0, p->ops.size(), (hipStream_t)stream, a);
+    }
+  });
+}
+
 // The engine sizes every Downsample output as floor(H / 2) x floor(W / 2) where torch's stride-2 conv gives the ceiling, and its
 // backward has no odd-size transposed conv: a map that does not survive the downsampling is refused, as unet_plan does.
 static void cls_need_divisible(df_ctx* c, int H, int W) {
@@ -539,6 +577,12 @@ int df_cfg_combine(const float* e2, float* e, int64_t n, float scale, void* stre
 }
 int df_lincomb(float* out, const float* const* in, const float* coef, int nterms, int64_t n, void* stream) {
   return guard([&] { HIPCHK(launch_lincomb(out, in, coef, nterms, (long)n, (hipStream_t)stream)); });
+}
+int df_posterior_sample(const float* moments, const float* noise, float* z, int B, int zc, int HW, float scale, void* stream) {
+  return guard([&] {
+    need_positive("posterior sample", {{"batch", B}, {"channels", zc}, {"H*W", HW}});
+    HIPCHK(launch_posterior_sample(moments, noise, z, B, zc, (long)HW, scale, (hipStream_t)stream));
+  });
 }
 int df_q_sample_blend(const float* img, const float* x0, const float* noise, const float* mask, float* out, int64_t n, int64_t chw,
                       int64_t hw, int mask_c, float sqrt_acp, float sqrt_one_minus_acp, void* stream) {

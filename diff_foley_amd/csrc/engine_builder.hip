@@ -70,10 +70,16 @@ Op& Builder::gemm(GemmParams gp, int batch, const char* tag) {
   if (gp.K % 64 != 0 || (gp.taps != 1 && gp.Cin % 64 != 0))
     fail("GEMM %s (%dx%dx%d, Cin %d): the contraction length must be a multiple of 64 (channel counts, context_dim and origin_dim "
          "that are not are outside what libdfengine builds)", tag, gp.M, gp.N, gp.K, gp.Cin);
-  choose_tile(gp.M, gp.N, gp.K, batch, gp.geglu != 0, &o.tile, &sk);
+  // batch-invariant plans (choice_NB): the choice is made for kChoiceBatch samples' rows (batched GEMMs: one matrix per sample)
+  int Mc = gp.M, bc = batch;
+  if (choice_NB > 0) {
+    if (batch == 1 && gp.M % choice_NB == 0) Mc = gp.M / choice_NB * kChoiceBatch;
+    if (batch > 1 && batch % choice_NB == 0) bc = batch / choice_NB * kChoiceBatch;
+  }
+  choose_tile(Mc, gp.N, gp.K, bc, gp.geglu != 0, &o.tile, &sk);
   if (gp.taps == 9 && gemm_tile_valid(gp, TILE_HALO_128x64, batch, 1)) {   // halo reuse beats re-fetching A per tap
     o.tile = TILE_HALO_128x64;
-    const long blocks = (long)((gp.M + 127) / 128) * ((gp.N + 63) / 64);
+    const long blocks = (long)((Mc + 127) / 128) * ((gp.N + 63) / 64);
     sk = 1;
     while (blocks * sk < 160 && sk < 16 && gp.Cin / 64 / (sk * 2) >= 2) sk *= 2;
   }
@@ -124,8 +130,15 @@ GemmParams Builder::gp_conv3(const bf16_t* A, int NB, int H, int Wd, int Cin, co
   g.OH = ups ? 2 * H : (stride == 2 ? H / 2 : H);
   g.OW = ups ? 2 * Wd : (stride == 2 ? Wd / 2 : Wd);
   g.M = NB * g.OH * g.OW; g.N = Cout; g.K = 9 * Cin;
-  g.taps = 9; g.Cin = Cin; g.alpha = 1.f;
+  g.taps = 9; g.Cin = Cin; g.alpha = 1.f; g.pad = 1;
   g.a_bytes = op_bytes((size_t)NB * H * Wd * Cin * 2); g.w_bytes = op_bytes((size_t)Cout * 9 * Cin * 2);
+  return g;
+}
+
+GemmParams Builder::gp_conv3_down_asym(const bf16_t* A, int NB, int H, int Wd, int Cin, const bf16_t* W, int Cout) {
+  if ((H | Wd) & 1) fail("asymmetric Downsample conv: the %dx%d map is not even", H, Wd);
+  GemmParams g = gp_conv3(A, NB, H, Wd, Cin, W, Cout, 2, 0);
+  g.pad = 0;
   return g;
 }
 

@@ -16,7 +16,7 @@
 // Builder, and the prototypes of every function one unit calls in another.  Who defines what:
 //   engine_pack.hip      df_ctx packers
 //   engine_builder.hip   choose_tile, Builder members
-//   engine_nets.hip      UNet topology, build_emb_table, build_unet_like, build_vae, build_cond, build_cavp
+//   engine_nets.hip      UNet topology, build_emb_table, build_unet_like, build_vae, build_vae_encoder, build_cond, build_cavp
 //   engine_cls_grad.hip  build_classifier_grad
 //   engine_run.hip       finish_plan, run_ops (+ debug hooks), get_plan, keyf
 //   engine_tune.hip      tune cache, apply_tune_cache, autotune_plan
@@ -132,6 +132,10 @@ struct Plan {
   // cfg.combine (op_cfgc) launches nothing while out.conv (op_outconv) runs split-K with the guided reduce
   bool tl_merged = false;
   long op_cfgc = -1, op_outconv = -1;
+  // The builder fixed every GEMM's tile and split-K as a function of the PER-SAMPLE problem (Builder::choice_NB): neither the tune
+  // table nor the autotuner may replace them (their entries are keyed by the row count, i.e. by the batch) -- VAE encoder plans,
+  // whose results must not depend on what else is in the batch
+  bool fixed_choices = false;
   std::string name;              // cache key (debug labels)
   void* chk_list = nullptr;      // debug checksums: device array of (pointer, 32-bit words) of every workspace block
   int chk_n = 0;
@@ -202,10 +206,11 @@ struct __attribute__((visibility("hidden"))) df_ctx {
   std::map<std::string, dfe::RawT> raw;
   std::map<std::string, void*> packed;
   std::vector<void*> packed_blocks;
-  bool has_unet = false, has_vae = false, has_cond = false, has_cls = false, has_cavp = false, finalized = false;
+  bool has_unet = false, has_vae = false, has_cond = false, has_cls = false, has_cavp = false, has_vae_enc = false, finalized = false;
   df_cavp_config pcfg{};
   df_unet_config ucfg{}, ccfg{};
   df_vae_config vcfg{};
+  df_vae_encoder_config ecfg{};
   df_cond_config kcfg{};
   std::map<std::string, int> emb_off[2];   // resblock prefix -> column offset in the fused emb projection
   int emb_total[2] = {0, 0};
@@ -367,6 +372,10 @@ struct Builder {
   // and leaves the buffer in last_aux.
   bool want_aux = false;
   bf16_t* last_aux = nullptr;
+  // > 0: the plan's batch size.  gemm() then chooses tile and split-K for kChoiceBatch samples of the problem whatever the batch is, so
+  // every sample's fp32 summation order -- and with it every bit of its result -- is the same in any batch (Plan::fixed_choices).
+  int choice_NB = 0;
+  static constexpr int kChoiceBatch = 4;
   void attach_aux(GemmParams& g, int rows, int C);
 
   template <class T>
@@ -390,6 +399,9 @@ struct Builder {
   static GemmParams gp_linear(const bf16_t* A, int M, int K, const bf16_t* W, int N);
   static GemmParams gp_conv3(const bf16_t* A, int NB, int H, int Wd, int Cin, const bf16_t* W, int Cout, int stride,
                              int ups);
+  // the VAE encoder's Downsample (stage1_autoencoder/model.py:167-171): F.pad(x, (0,1,0,1)) + stride-2 conv with padding 0 =
+  // gp_conv3(..., stride 2) with GemmParams::pad = 0 (H and Wd even)
+  static GemmParams gp_conv3_down_asym(const bf16_t* A, int NB, int H, int Wd, int Cin, const bf16_t* W, int Cout);
   // nearest-x2 upsample + conv3x3 as four 2x2-tap convs (one per output phase) over the INPUT-resolution map: rows = input
   // pixels, K = 4 Cin, one weight matrix per phase (w_bs), output rows = the x2 map (the kernel scatters by phase)
   static GemmParams gp_conv3_ups4(const bf16_t* A, int NB, int H, int Wd, int Cin, const bf16_t* W4, int Cout);
@@ -437,6 +449,10 @@ void build_emb_table(df_ctx* c, int which);
 void build_unet_like(df_ctx* c, Plan* pl, int which, int N, int H, int W, int Tc, bool cfg_mode);
 void build_classifier_grad(df_ctx* c, Plan* pl, int N, int H, int W, int Tc);
 void build_vae(df_ctx* c, Plan* pl, int B, int H, int W);
+// tap >= 0 (df_test_vae_encode_tap): one stage's fp32 output is also copied to RunArgs.out2 -- 0 conv_in, 1 + l Downsample l, 100 mid
+void build_vae_encoder(df_ctx* c, Plan* pl, int B, int H, int W, int tap = -1);
+// every state_dict key the encoder plan reads (df_finalize requires them once the encoder is configured)
+std::vector<std::string> vae_encoder_tensor_names(const df_ctx* c);
 void build_cond(df_ctx* c, Plan* pl, int B, int T);
 void build_cavp(df_ctx* c, Plan* pl, int T, int H, int W);
 

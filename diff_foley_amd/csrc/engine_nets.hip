@@ -1,5 +1,5 @@
 // libdfengine: UNet topology and the forward plans of the four networks -- UNet / classifier backbone, VAE decoder, cond stage,
-// CAVP video encoder (types and the Builder: engine_internal.h).
+// VAE encoder, CAVP video encoder (types and the Builder: engine_internal.h).
 #include "engine_internal.h"
 
 DFE_NAMESPACE {
@@ -358,6 +358,82 @@ void build_unet_like(df_ctx* c, Plan* pl, int which, int N, int H, int W, int Tc
   }
 }
 
+// AttnBlock (stage1_autoencoder/model.py:273-297) of the VAE's mid section, decoder and encoder alike: a single head over T = hh * ww
+// tokens with head dim = ch -> GEMM + row-softmax + GEMM.  p: the block's state_dict prefix below b.pre; t: the op tags of the plan it
+// is built into.  Consumes h (released) and returns the block's output.
+struct VaeAttnTags { const char *q, *k, *vT_pad, *vT, *qk, *softmax, *pv, *proj_out; };
+static const VaeAttnTags kVaeDecAttn{"vae.q", "vae.k", "vae.vT.pad", "vae.vT", "vae.qk", "vae.softmax", "vae.pv", "vae.proj_out"};
+static const VaeAttnTags kVaeEncAttn{"vaeenc.q", "vaeenc.k", "vaeenc.vT.pad", "vaeenc.vT", "vaeenc.qk", "vaeenc.softmax", "vaeenc.pv",
+                                     "vaeenc.proj_out"};
+static F32 vae_attn_block(Builder& b, const std::string& p, F32 h, int B, int T, const VaeAttnTags& t) {
+  df_ctx* c = b.c;
+  Plan* pl = b.pl;
+  const std::string& pre = b.pre;
+  const int ch = h.C, M = B * T;
+  // the P V contraction runs over the tokens: padded to whole 64-element K steps (zero probabilities against zeroed V^T columns)
+  // for maps whose token count is not a multiple of 64 (any latent but the 16 x 64 one may be: decode_first_stage takes them all)
+  const int Tp = rup(T, 64);
+  bf16_t* a = b.groupnorm(h, B, p + ".norm", 1e-6f, 0, nullptr);
+  bf16_t* q = b.buf<bf16_t>((size_t)M * ch);
+  bf16_t* k = b.buf<bf16_t>((size_t)M * ch);
+  bf16_t* vt = b.buf<bf16_t>((size_t)B * ch * Tp);
+  {
+    GemmParams g = Builder::gp_linear(a, M, ch, c->w_linear(pre + p + ".q.weight"), ch);
+    Builder::out_b16(g, q, ch);
+    g.bias = c->f32(pre + p + ".q.bias");
+    b.gemm(g, 1, t.q);
+  }
+  {
+    GemmParams g = Builder::gp_linear(a, M, ch, c->w_linear(pre + p + ".k.weight"), ch);
+    Builder::out_b16(g, k, ch);
+    g.bias = c->f32(pre + p + ".k.bias");
+    b.gemm(g, 1, t.k);
+  }
+  {  // V^T without its bias: softmax rows sum to 1, so P(V + 1 b^T) = P V + b^T -> bias added after P V
+    if (Tp != T) {
+      const size_t nb = (size_t)B * ch * Tp * sizeof(bf16_t);
+      b.other(t.vT_pad, [=](hipStream_t s, const RunArgs&) { return hipMemsetAsync(vt, 0, nb, s); });
+    }
+    GemmParams g = Builder::gp_linear(c->w_linear(pre + p + ".v.weight"), ch, ch, a, T);
+    g.w_bs = (long)T * ch;
+    Builder::out_b16(g, vt, Tp);
+    g.c_bs = (long)ch * Tp;
+    b.gemm(g, B, t.vT);
+  }
+  float* sc = b.buf<float>((size_t)B * T * T);
+  {
+    GemmParams g = Builder::gp_linear(q, T, ch, k, T);
+    g.a_bs = (long)T * ch;
+    g.w_bs = (long)T * ch;
+    Builder::out_f32(g, sc, T);
+    g.c_bs = (long)T * T;
+    g.alpha = 1.0f / sqrtf((float)ch);
+    b.gemm(g, B, t.qk);
+  }
+  bf16_t* pr = b.buf<bf16_t>((size_t)B * T * Tp);
+  b.other(t.softmax, [=](hipStream_t s, const RunArgs&) { return launch_softmax_rows(sc, pr, B * T, T, Tp, s); });
+  bf16_t* o = q;
+  {
+    GemmParams g = Builder::gp_linear(pr, T, Tp, vt, ch);
+    g.a_bs = (long)T * Tp;
+    g.w_bs = (long)ch * Tp;
+    Builder::out_b16(g, o, ch);
+    g.c_bs = (long)T * ch;
+    g.bias = c->f32(pre + p + ".v.bias");
+    b.gemm(g, B, t.pv);
+  }
+  F32 ho{b.buf<float>((size_t)M * ch), M, ch, ch};
+  {
+    GemmParams g = Builder::gp_linear(o, M, ch, c->w_linear(pre + p + ".proj_out.weight"), ch);
+    Builder::out_f32(g, ho.p, ch);
+    g.bias = c->f32(pre + p + ".proj_out.bias");
+    g.res = h.p; g.ldr = h.ld;
+    b.gemm(g, 1, t.proj_out);
+  }
+  for (void* p_ : {(void*)a, (void*)q, (void*)k, (void*)vt, (void*)sc, (void*)pr, (void*)h.p}) pl->release(p_);
+  return ho;
+}
+
 // VAE decoder plan (autoencoder.py:330-333, stage1_autoencoder/model.py:630-663)
 void build_vae(df_ctx* c, Plan* pl, int B, int H, int W) {
   const df_vae_config& v = c->vcfg;
@@ -392,72 +468,7 @@ void build_vae(df_ctx* c, Plan* pl, int B, int H, int W) {
     return o;
   };
   h = res("decoder.mid.block_1", h, ch);
-  {  // AttnBlock (model.py:273-297): single head over hh*ww tokens, head dim = ch -> GEMM + row-softmax + GEMM
-    const std::string p = "decoder.mid.attn_1";
-    const int T = hh * ww, M = B * T;
-    // the P V contraction runs over the tokens: padded to whole 64-element K steps (zero probabilities against zeroed V^T columns)
-    // for maps whose token count is not a multiple of 64 (any latent but the 16 x 64 one may be: decode_first_stage takes them all)
-    const int Tp = rup(T, 64);
-    bf16_t* a = b.groupnorm(h, B, p + ".norm", 1e-6f, 0, nullptr);
-    bf16_t* q = b.buf<bf16_t>((size_t)M * ch);
-    bf16_t* k = b.buf<bf16_t>((size_t)M * ch);
-    bf16_t* vt = b.buf<bf16_t>((size_t)B * ch * Tp);
-    {
-      GemmParams g = Builder::gp_linear(a, M, ch, c->w_linear(pre + p + ".q.weight"), ch);
-      Builder::out_b16(g, q, ch);
-      g.bias = c->f32(pre + p + ".q.bias");
-      b.gemm(g, 1, "vae.q");
-    }
-    {
-      GemmParams g = Builder::gp_linear(a, M, ch, c->w_linear(pre + p + ".k.weight"), ch);
-      Builder::out_b16(g, k, ch);
-      g.bias = c->f32(pre + p + ".k.bias");
-      b.gemm(g, 1, "vae.k");
-    }
-    {  // V^T without its bias: softmax rows sum to 1, so P(V + 1 b^T) = P V + b^T -> bias added after P V
-      if (Tp != T) {
-        const size_t nb = (size_t)B * ch * Tp * sizeof(bf16_t);
-        b.other("vae.vT.pad", [=](hipStream_t s, const RunArgs&) { return hipMemsetAsync(vt, 0, nb, s); });
-      }
-      GemmParams g = Builder::gp_linear(c->w_linear(pre + p + ".v.weight"), ch, ch, a, T);
-      g.w_bs = (long)T * ch;
-      Builder::out_b16(g, vt, Tp);
-      g.c_bs = (long)ch * Tp;
-      b.gemm(g, B, "vae.vT");
-    }
-    float* sc = b.buf<float>((size_t)B * T * T);
-    {
-      GemmParams g = Builder::gp_linear(q, T, ch, k, T);
-      g.a_bs = (long)T * ch;
-      g.w_bs = (long)T * ch;
-      Builder::out_f32(g, sc, T);
-      g.c_bs = (long)T * T;
-      g.alpha = 1.0f / sqrtf((float)ch);
-      b.gemm(g, B, "vae.qk");
-    }
-    bf16_t* pr = b.buf<bf16_t>((size_t)B * T * Tp);
-    b.other("vae.softmax", [=](hipStream_t s, const RunArgs&) { return launch_softmax_rows(sc, pr, B * T, T, Tp, s); });
-    bf16_t* o = q;
-    {
-      GemmParams g = Builder::gp_linear(pr, T, Tp, vt, ch);
-      g.a_bs = (long)T * Tp;
-      g.w_bs = (long)ch * Tp;
-      Builder::out_b16(g, o, ch);
-      g.c_bs = (long)T * ch;
-      g.bias = c->f32(pre + p + ".v.bias");
-      b.gemm(g, B, "vae.pv");
-    }
-    F32 ho{b.buf<float>((size_t)M * ch), M, ch, ch};
-    {
-      GemmParams g = Builder::gp_linear(o, M, ch, c->w_linear(pre + p + ".proj_out.weight"), ch);
-      Builder::out_f32(g, ho.p, ch);
-      g.bias = c->f32(pre + p + ".proj_out.bias");
-      g.res = h.p; g.ldr = h.ld;
-      b.gemm(g, 1, "vae.proj_out");
-    }
-    for (void* p_ : {(void*)a, (void*)q, (void*)k, (void*)vt, (void*)sc, (void*)pr, (void*)h.p}) pl->release(p_);
-    h = ho;
-  }
+  h = vae_attn_block(b, "decoder.mid.attn_1", h, B, hh * ww, kVaeDecAttn);
   h = res("decoder.mid.block_2", h, ch);
   for (int lvl = v.n_mult - 1; lvl >= 0; --lvl) {
     const int co = v.ch * v.ch_mult[lvl];
@@ -493,6 +504,128 @@ void build_vae(df_ctx* c, Plan* pl, int B, int H, int W) {
   g.hw_out = hh * ww;
   Op& o = b.gemm(g, 1, "vae.conv_out");
   o.c_ext = true;
+}
+
+// VAE encoder plan: quant_conv(encoder(x)) (autoencoder.py:324-328, stage1_autoencoder/model.py:529-554).  The decoder's mirror image:
+// conv_in from the <= 4 image channels (conv3x3_fewin), per level num_res_blocks ResnetBlocks and -- on every level but the last -- the
+// asymmetrically padded stride-2 Downsample (model.py:167-171, gp_conv3_down_asym), mid block_1 / attn_1 / block_2, norm_out + SiLU,
+// conv_out, and quant_conv as a second small fp32 op that writes the moments NCHW.
+void build_vae_encoder(df_ctx* c, Plan* pl, int B, int H, int W, int tap) {
+  const df_vae_config& v = c->vcfg;
+  const std::string pre = "first_stage_model.";
+  Builder b{c, pl, pre, 0};
+  const int zc = v.z_channels, cin = c->ecfg.in_channels;
+  if (zc < 1 || zc > 64 || v.embed_dim != zc)
+    fail("vae encoder: z_channels = %d, embed_dim = %d: built for embed_dim == z_channels, 1 .. 64 (as the decoder)", zc, v.embed_dim);
+  if (cin < 1 || cin > 4) fail("vae encoder: in_channels = %d: conv_in is built for 1 .. 4 image channels", cin);
+  // The latent of a clip must not depend on its batch-mates (x0 of an inpainting call; the decoder's and the UNet's tables are keyed by
+  // the row count, so their summation order follows the batch): every GEMM choice is a function of the per-sample problem
+  b.choice_NB = B;
+  pl->fixed_choices = true;
+  int hh = H, ww = W;
+  int ch = v.ch;
+  F32 h{b.buf<float>((size_t)B * hh * ww * ch), B * hh * ww, ch, ch};
+  {
+    if (!conv3x3_fewin_ok(hh, ww, cin, ch, ch)) fail("vae encoder: no conv_in kernel for %d -> %d channels", cin, ch);
+    const float* wi = c->f32(pre + "encoder.conv_in.weight");
+    const float* bi = c->f32(pre + "encoder.conv_in.bias");
+    float* o = h.p;
+    const int H_ = hh, W_ = ww, C_ = ch;
+    pl->ext_hint = std::max(pl->ext_hint, (size_t)B * cin * H * W * 4);
+    b.other("vaeenc.conv_in", [=](hipStream_t s, const RunArgs& a) { return launch_conv3x3_fewin(a.x, wi, bi, o, C_, B, H_, W_, cin, C_, s); });
+  }
+  auto tap_here = [&](int id, const F32& x) {      // tests only: the stage's rows leave the plan as they are at this point
+    if (tap != id) return;
+    const float* src = x.p;
+    const size_t bytes = (size_t)x.rows * x.C * sizeof(float);
+    b.other("vaeenc.tap", [=](hipStream_t s, const RunArgs& ra) {
+      return ra.out2 ? hipMemcpyAsync(ra.out2, src, bytes, hipMemcpyDeviceToDevice, s) : hipSuccess;
+    });
+  };
+  tap_here(0, h);
+  auto res = [&](const std::string& p, F32 x, int cout) {
+    F32 o{b.buf<float>((size_t)x.rows * cout), x.rows, cout, cout};
+    b.resblock(x, o, B, hh, ww, p + ".norm1", p + ".conv1", p + ".norm2", p + ".conv2", p + ".nin_shortcut", 1e-6f,
+               nullptr, 0, 0);
+    pl->release(x.p);
+    return o;
+  };
+  for (int lvl = 0; lvl < v.n_mult; ++lvl) {
+    const int co = v.ch * v.ch_mult[lvl];
+    const bool down = lvl != v.n_mult - 1;
+    bf16_t* hb = nullptr;
+    for (int ib = 0; ib < v.num_res_blocks; ++ib) {
+      // the Downsample conv reads the operand-type copy of the level's last ResnetBlock output: written by that block's conv2
+      b.want_aux = down && ib == v.num_res_blocks - 1;
+      h = res("encoder.down." + std::to_string(lvl) + ".block." + std::to_string(ib), h, co);
+      hb = b.last_aux;
+      b.last_aux = nullptr;
+      b.want_aux = false;
+    }
+    ch = co;
+    if (down) {
+      if (!hb) hb = b.cast2d(h);
+      F32 o{b.buf<float>((size_t)(h.rows / 4) * co), h.rows / 4, co, co};
+      const std::string p = pre + "encoder.down." + std::to_string(lvl) + ".downsample.conv";
+      GemmParams g = Builder::gp_conv3_down_asym(hb, B, hh, ww, co, c->w_conv3(p + ".weight", co), co);
+      Builder::out_f32(g, o.p, co);
+      g.bias = c->f32(p + ".bias");
+      b.gemm(g, 1, "vaeenc.down");
+      pl->release(hb);
+      pl->release(h.p);
+      h = o;
+      hh /= 2;
+      ww /= 2;
+      tap_here(1 + lvl, h);
+    }
+  }
+  h = res("encoder.mid.block_1", h, ch);
+  h = vae_attn_block(b, "encoder.mid.attn_1", h, B, hh * ww, kVaeEncAttn);
+  h = res("encoder.mid.block_2", h, ch);
+  tap_here(100, h);
+  bf16_t* a = b.groupnorm(h, B, "encoder.norm_out", 1e-6f, 1, nullptr);
+  float* m = b.buf<float>((size_t)h.rows * 2 * zc);
+  {
+    GemmParams g = Builder::gp_conv3(a, B, hh, ww, ch, c->w_conv3(pre + "encoder.conv_out.weight", ch), 2 * zc, 1, 0);
+    Builder::out_f32(g, m, 2 * zc);
+    g.bias = c->f32(pre + "encoder.conv_out.bias");
+    b.gemm(g, 1, "vaeenc.conv_out");
+  }
+  {
+    const float* wq = c->f32(pre + "quant_conv.weight");
+    const float* bq = c->f32(pre + "quant_conv.bias");
+    const int HW = hh * ww, ci = 2 * zc, co = 2 * v.embed_dim;
+    b.other("vaeenc.quant_conv", [=](hipStream_t s, const RunArgs& ra) { return launch_conv1x1_rows_nchw(m, ci, wq, bq, ra.out, B, HW, ci, co, s); });
+  }
+}
+
+std::vector<std::string> vae_encoder_tensor_names(const df_ctx* c) {
+  const df_vae_config& v = c->vcfg;
+  std::vector<std::string> r;
+  const std::string e = "first_stage_model.encoder.";
+  auto wb = [&](const std::string& p) { r.push_back(p + ".weight"); r.push_back(p + ".bias"); };
+  auto resn = [&](const std::string& p, int ci, int co) {
+    wb(p + ".norm1"); wb(p + ".conv1"); wb(p + ".norm2"); wb(p + ".conv2");
+    if (ci != co) wb(p + ".nin_shortcut");
+  };
+  wb(e + "conv_in");
+  int ch = v.ch;
+  for (int lvl = 0; lvl < v.n_mult; ++lvl) {
+    const int co = v.ch * v.ch_mult[lvl];
+    for (int ib = 0; ib < v.num_res_blocks; ++ib) {
+      resn(e + "down." + std::to_string(lvl) + ".block." + std::to_string(ib), ch, co);
+      ch = co;
+    }
+    if (lvl != v.n_mult - 1) wb(e + "down." + std::to_string(lvl) + ".downsample.conv");
+  }
+  resn(e + "mid.block_1", ch, ch);
+  wb(e + "mid.attn_1.norm");
+  for (const char* n : {"q", "k", "v", "proj_out"}) wb(e + "mid.attn_1." + n);
+  resn(e + "mid.block_2", ch, ch);
+  wb(e + "norm_out");
+  wb(e + "conv_out");
+  wb("first_stage_model.quant_conv");
+  return r;
 }
 
 // cond stage: Linear(origin->embed) + pos_emb[:T]  (video_feat_encoder.py:12-18)

@@ -211,7 +211,8 @@ Plan* get_plan(df_ctx* c, const std::string& key, const std::function<void(Plan*
   }
   std::unique_ptr<Plan> p(new Plan());
   build(p.get());
-  if (c->autotune || g_tune_imported) {
+  const bool tunable = !p->fixed_choices;
+  if (tunable && (c->autotune || g_tune_imported)) {
     // tuning may try larger split-K factors than the cost model picked: give the scratch some head-room
     size_t want = 0;
     for (auto& o : p->ops)
@@ -220,7 +221,8 @@ Plan* get_plan(df_ctx* c, const std::string& key, const std::function<void(Plan*
     if (want > p->partial_bytes) p->partial_bytes = want;
   }
   finish_plan(c, p.get());
-  if (c->autotune) {
+  if (!tunable) {
+  } else if (c->autotune) {
     autotune_plan(c, p.get(), c->pack_stream);
     HIPCHK(hipStreamSynchronize(c->pack_stream));
   } else if (g_tune_imported) {

@@ -475,6 +475,82 @@ int df_test_conv3x3_fewout(const uint16_t* A, const uint16_t* W, const float* bi
   return guard([&] { HIPCHK(launch_conv3x3_fewout(A, W, bias, out_nchw, NB, H, Wd, Cin, Cout, (hipStream_t)stream)); });
 }
 
+int df_test_conv3x3_fewin(const float* x, const float* W, const float* bias, float* out, int ldo, int NB, int H, int Wd, int Cin, int Cout,
+                          void* stream) {
+  return guard([&] {
+    if (!conv3x3_fewin_ok(H, Wd, Cin, Cout, ldo) || NB <= 0) fail("conv3x3_fewin: %d -> %d channels on %dx%d, ld %d is refused", Cin, Cout, H, Wd, ldo);
+    HIPCHK(launch_conv3x3_fewin(x, W, bias, out, ldo, NB, H, Wd, Cin, Cout, (hipStream_t)stream));
+  });
+}
+
+// the route conv3x3_fewin replaces: NCHW fp32 -> 64 operand-type channels, weights packed to [Cout][3][3][64], implicit GEMM on the
+// tile Builder::gemm would choose (halo where it fits, else the cost model)
+int df_test_conv3x3_fewin_gemm(const float* x, const float* W, const float* bias, float* out, uint16_t* xpad, uint16_t* wpad, int NB, int H,
+                               int Wd, int Cin, int Cout, void* stream) {
+  return guard([&] {
+    hipStream_t s = (hipStream_t)stream;
+    if (Cin < 1 || Cin > 64 || NB <= 0 || H <= 0 || Wd <= 0) fail("conv3x3_fewin_gemm: bad shape");
+    HIPCHK(launch_pack_latent(x, xpad, NB, Cin, H * Wd, 64, 1, 1.0f, nullptr, nullptr, s));
+    HIPCHK(launch_pack_conv_weight(W, wpad, Cout, Cin, 3, 3, 64, s));
+    Plan pl;
+    Builder b{nullptr, &pl, "", 0};
+    GemmParams g = Builder::gp_conv3(xpad, NB, H, Wd, 64, wpad, Cout, 1, 0);
+    Builder::out_f32(g, out, Cout);
+    g.bias = bias;
+    const Op& o = b.gemm(g, 1, "conv_in");
+    GemmParams gp = o.gp;
+    if (gp.splitk > 1) gp.partial = test_partial((size_t)gp.splitk * gp.M * gp.N * 4);
+    test_launch_gemm(gp, o.tile, 1, s);
+  });
+}
+
+int df_test_vae_encode_tap(df_ctx* c, const float* x, float* moments, float* tap_out, int tap, int B, int H, int W, void* stream) {
+  return guard([&] {
+    if (!c->has_vae || !c->has_vae_enc) fail("vae encoder not configured");
+    const int f = 1 << (c->vcfg.n_mult - 1);
+    if (B <= 0 || B > 16 || H <= 0 || W <= 0 || H % f || W % f || tap < 0) fail("vae encode tap: bad shape %d x %dx%d / tap %d", B, H, W, tap);
+    Plan* p = get_plan(c, keyf("vaeenc_tap%d_%d_%d_%d", tap, B, H, W), [&](Plan* pl) { build_vae_encoder(c, pl, B, H, W, tap); });
+    RunArgs a;
+    a.x = x;
+    a.out = moments;
+    a.out2 = tap_out;
+    run_ops(c, p, 0, p->ops.size(), (hipStream_t)stream, a);
+  });
+}
+
+static GemmParams test_down_params(const uint16_t* A, const uint16_t* W, const float* bias, float* C, int NB, int H, int Wd, int Cin,
+                                   int Cout, int pad, int splitk) {
+  if (pad != 0 && pad != 1) fail("conv3x3_down: pad %d", pad);
+  if (NB <= 0 || H <= 0 || Wd <= 0 || ((H | Wd) & 1)) fail("conv3x3_down: a positive even map, got %d x %dx%d", NB, H, Wd);
+  GemmParams g = pad ? Builder::gp_conv3(A, NB, H, Wd, Cin, W, Cout, 2, 0) : Builder::gp_conv3_down_asym(A, NB, H, Wd, Cin, W, Cout);
+  Builder::out_f32(g, C, Cout);
+  g.bias = bias;
+  g.splitk = splitk > 1 ? splitk : 1;
+  return g;
+}
+
+int df_test_conv3x3_down(const uint16_t* A, const uint16_t* W, const float* bias, float* C, int NB, int H, int Wd, int Cin, int Cout,
+                         int pad, int tile, int splitk, void* stream) {
+  return guard([&] {
+    GemmParams g = test_down_params(A, W, bias, C, NB, H, Wd, Cin, Cout, pad, splitk);
+    if (g.K % 64 != 0 || g.Cin % 64 != 0) fail("conv3x3_down: Cin %d is not a multiple of 64", Cin);
+    if (g.splitk > 1) g.partial = test_partial((size_t)g.splitk * g.M * g.N * 4);
+    test_launch_gemm(g, tile, 1, (hipStream_t)stream);
+  });
+}
+
+int df_test_conv3x3_down_valid(int NB, int H, int Wd, int Cin, int Cout, int pad, int tile, int splitk) {
+  std::lock_guard<std::recursive_mutex> hold(g_api_lock);
+  try {
+    const GemmParams g = test_down_params(nullptr, nullptr, nullptr, nullptr, NB, H, Wd, Cin, Cout, pad, splitk);
+    if (g.K % 64 != 0 || g.Cin % 64 != 0) return 0;
+    return gemm_route(g, tile, 1, splitk, nullptr) ? 0 : 1;
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return 0;
+  }
+}
+
 // Which kernel form a shape takes (host only; csrc/kernels.h groupnorm_form / attention_form -- the functions the launchers
 // themselves dispatch on): tests/test_kernel_forms_cpu.py asserts that the GPU tests' shape tables reach every form.
 int df_test_groupnorm_form(int N, int HW, int C, int nslab) { return groupnorm_form(N, HW, C, nslab); }

@@ -27,6 +27,8 @@ struct GemmParams {
   int H, Wd;   // stored input spatial size
   int OH, OW;  // output spatial size (M = batch * OH * OW)
   int stride;  // 1 | 2
+  int pad;     // taps == 9, MODE 2 (stride 2 / upsampled input): zero padding in front of row 0 / column 0 -- 1 = the symmetric conv, 0 = the VAE
+               // encoder's Downsample (F.pad(x, (0,1,0,1)) + a padding-0 conv: only the bottom row and the right column read zeros)
   int ups;     // 1: conv runs on the nearest-x2 upsampled input
   int zstuff;  // with ups=1: the x2 input is ZERO-stuffed (transposed stride-2 conv, backward of Downsample), not nearest
   int th, tw;  // halo kernels: spatial patch of output pixels owned per block (th*tw divides BM)

@@ -245,6 +245,8 @@ const char* gemm_route(const GemmParams& p, int tile, int batch, int splitk, Gem
   r.zdim = sk > 1 ? sk : (batch > 0 ? batch : 1);
   // which (tile, MODE) pairs are built: gemm_tiles.def M0 .. M3 (a retired id: none)
   if (!((t.modes >> r.mode) & 1)) return "this tile is not built for the problem's MODE";
+  if (p.taps == 9 && p.pad != 1 && (p.pad != 0 || r.mode != 2 || p.stride != 2 || p.ups))
+    return "pad: 1 for every 3x3 conv, 0 only for the stride-2 conv of an asymmetrically padded Downsample";
   if (t.family == DF_FAM_PGEGLU || t.family == DF_FAM_WGEGLU) {
     if (const char* no = route_fused_geglu(p, t, batch, sk)) return no;
     r.epi = EPI_GEGLU;

@@ -722,8 +722,8 @@ __device__ __forceinline__ void gemm_bf16_body(const GemmParams& p) {
         a_msk[i] = msk;
       } else {
         a_off[i] = (unsigned)(nb * p.H * p.Wd);
-        a_iy[i] = mv ? oy * p.stride - 1 : -(1 << 20);
-        a_ix[i] = ox * p.stride - 1;
+        a_iy[i] = mv ? oy * p.stride - p.pad : -(1 << 20);
+        a_ix[i] = ox * p.stride - p.pad;
       }
     }
   }

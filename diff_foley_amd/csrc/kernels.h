@@ -54,6 +54,19 @@ bool conv3x3_fewout_ok(int H, int W, int C, int Cout);
 hipError_t launch_conv3x3_fewout(const uint16_t* X, const uint16_t* Wt /*[Cout][9][C]*/, const float* bias, float* out, int NB, int H, int W,
                                  int C, int Cout, hipStream_t s);
 
+// 3x3 convolution (stride 1, zero padding 1) from <= 4 input channels: NCHW fp32 input -> fp32 NHWC rows [NB*H*W][ldo] (elementwise.hip;
+// the VAE encoder's conv_in).  Wt is the checkpoint's OIHW fp32 weight; fp32 VALU arithmetic, inputs and weights are NOT rounded.
+bool conv3x3_fewin_ok(int H, int W, int Cin, int Cout, int ldo);
+hipError_t launch_conv3x3_fewin(const float* X /*[NB][Cin][H][W]*/, const float* Wt /*[Cout][Cin][3][3]*/, const float* bias, float* out,
+                                int ldo, int NB, int H, int W, int Cin, int Cout, hipStream_t s);
+// 1x1 conv of fp32 NHWC rows to an fp32 NCHW tensor: out[b][o][hw] = bq[o] + sum_i Wq[o][i] * h[(b*HW + hw)*ld + i]  (the VAE's
+// quant_conv behind the encoder's conv_out; Cin, Cout <= 128)
+hipError_t launch_conv1x1_rows_nchw(const float* h, int ld, const float* Wq, const float* bq, float* out, int B, int HW, int Cin,
+                                    int Cout, hipStream_t s);
+// DiagonalGaussianDistribution.sample() * scale: z = scale * (mean + exp(0.5 * clamp(logvar, -30, 20)) * noise) with moments
+// [B][2*zc][HW] = (mean | logvar), z / noise [B][zc][HW]; noise == nullptr: z = scale * mean (mode())
+hipError_t launch_posterior_sample(const float* moments, const float* noise, float* z, int B, int zc, long HW, float scale, hipStream_t s);
+
 // Row softmax: fp32 scores [rows][T] -> bf16 probabilities [rows][T]  (VAE single-head attention)
 // p rows have ldp >= T elements; columns [T, ldp) are written as zeros (the K padding of the P V GEMM)
 hipError_t launch_softmax_rows(const float* s, uint16_t* p, int rows, int T, int ldp, hipStream_t st);

@@ -78,6 +78,10 @@ class VaeConfig(C.Structure):
                 ("out_ch", C.c_int), ("ch_mult", C.c_int * 8), ("n_mult", C.c_int), ("scale_factor", C.c_float)]
 
 
+class VaeEncoderConfig(C.Structure):
+    _fields_ = [("in_channels", C.c_int)]
+
+
 class CondConfig(C.Structure):
     _fields_ = [("origin_dim", C.c_int), ("embed_dim", C.c_int), ("seq_len", C.c_int)]
 
@@ -93,6 +97,7 @@ _SIGS = {
     "df_config_unet": [C.c_void_p, C.POINTER(UNetConfig)],
     "df_config_vae": [C.c_void_p, C.POINTER(VaeConfig)],
     "df_config_cond": [C.c_void_p, C.POINTER(CondConfig)],
+    "df_config_vae_encoder": [C.c_void_p, C.POINTER(VaeEncoderConfig)],
     "df_config_cavp": [C.c_void_p, C.POINTER(CavpConfig)],
     "df_cavp_encode": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p],
     "df_cavp_pool": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p],
@@ -111,6 +116,8 @@ _SIGS = {
     "df_unet_forward_cfg_ts": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float,
                                C.c_void_p],
     "df_vae_decode": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p],
+    "df_vae_encode": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p],
+    "df_posterior_sample": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p],
     "df_classifier_forward": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                               C.c_int, C.c_void_p],
     "df_classifier_grad": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
@@ -146,6 +153,11 @@ _SIGS = {
                       C.c_int, C.c_void_p],
     "df_test_scratch_read": [C.c_void_p, C.c_int64],
     "df_test_conv3x3_fewout": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p],
+    "df_test_conv3x3_fewin": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p],
+    "df_test_conv3x3_fewin_gemm": [C.c_void_p] * 6 + [C.c_int] * 5 + [C.c_void_p],
+    "df_test_vae_encode_tap": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p],
+    "df_test_conv3x3_down": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 8 + [C.c_void_p],
+    "df_test_conv3x3_down_valid": [C.c_int] * 8,
     "df_debug_saturations": [C.c_void_p, C.c_int, C.c_int64],
     "df_debug_saturations_read": [C.c_void_p, C.POINTER(C.c_uint64), C.c_int64, C.POINTER(C.c_int64)],
     "df_debug_saturation_label": [C.c_void_p, C.c_int64, C.c_char_p, C.c_int64],
@@ -399,6 +411,16 @@ class Engine:
         v.scale_factor = float(scale_factor)
         _chk(self.L.df_config_vae(self._h, C.byref(v)), self.L)
 
+    def config_vae_encoder(self, cfg):
+        """cfg: dict(in_channels=...) with the encoder's tensors about to be loaded, or None: no encoder (encode raises)."""
+        if cfg is None:
+            _chk(self.L.df_config_vae_encoder(self._h, None), self.L)
+            self.vae_in_channels = None
+            return
+        e = VaeEncoderConfig(int(cfg["in_channels"]))
+        _chk(self.L.df_config_vae_encoder(self._h, C.byref(e)), self.L)
+        self.vae_in_channels = int(cfg["in_channels"])
+
     def config_cond(self, cfg):
         k = CondConfig(cfg["origin_dim"], cfg["embed_dim"], cfg["seq_len"])
         _chk(self.L.df_config_cond(self._h, C.byref(k)), self.L)
@@ -566,6 +588,32 @@ class Engine:
         _chk(self.L.df_vae_decode(self._h, _ptr(z), _ptr(out), B, H, W, self._on("vae")), self.L)
         return out
 
+    def vae_encode(self, x):
+        """x [B][in_channels][H][W] -> moments [B][2*embed_dim][H/f][W/f] = quant_conv(encoder(x)) (df_vae_encode)."""
+        x = _dev_f32(x, self.device)
+        _want_nchw("encode_first_stage: image", x, getattr(self, "vae_in_channels", None))
+        B, Cc, H, W = x.shape
+        f = 2 ** (self.vae_n_mult - 1)
+        if H <= 0 or W <= 0 or H % f or W % f:
+            raise RuntimeError(f"encode_first_stage: image {H}x{W} is not a positive multiple of the encoder's downsampling ({f}) "
+                               "(the reference floors such maps; this engine refuses them)")
+        out = torch.empty(B, 2 * self.vae_embed_dim, H // f, W // f, device=self.device, dtype=torch.float32)
+        if B == 0:
+            return out
+        _chk(self.L.df_vae_encode(self._h, _ptr(x), _ptr(out), B, H, W, self._on("vaeenc")), self.L)
+        return out
+
+    def vae_encode_tap(self, x, tap, tap_hwc):
+        """Tests: (moments, one intermediate stage as NCHW) of vae_encode -- df_test_vae_encode_tap; tap_hwc = (h, w, C) of the stage."""
+        x = _dev_f32(x, self.device)
+        B, Cc, H, W = x.shape
+        f = 2 ** (self.vae_n_mult - 1)
+        out = torch.empty(B, 2 * self.vae_embed_dim, H // f, W // f, device=self.device, dtype=torch.float32)
+        h, w, ch = tap_hwc
+        stage = torch.empty(B, h, w, ch, device=self.device, dtype=torch.float32)
+        _chk(self.L.df_test_vae_encode_tap(self._h, _ptr(x), _ptr(out), _ptr(stage), int(tap), B, H, W, self._on("vaeenc")), self.L)
+        return out, stage.permute(0, 3, 1, 2).contiguous()
+
     def classifier_forward(self, x, t, feat):
         x = _dev_f32(x, self.device)
         feat = _dev_f32(feat, self.device)
@@ -725,6 +773,25 @@ def lincomb(terms, out=None):
     coefs = (C.c_float * n)(*[float(c) for c, _ in terms])
     _chk(lib().df_lincomb(_ptr(out), ptrs, coefs, n, out.numel(), _stream()))
     return out
+
+
+def posterior_sample(moments, noise=None, scale=1.0):
+    """scale * (mean + exp(0.5 * clamp(logvar, -30, 20)) * noise) for moments [B][2 zc][H][W] = (mean | logvar), noise [B][zc][H][W]
+    (DiagonalGaussianDistribution.sample, stage1_autoencoder/model.py:38-47); noise None: scale * mean."""
+    B, c2, H, W = moments.shape
+    if c2 % 2:
+        raise ValueError(f"posterior parameters with {c2} channels (mean | logvar need an even count)")
+    moments = moments.contiguous()
+    z = torch.empty(B, c2 // 2, H, W, device=moments.device, dtype=torch.float32)
+    if z.numel() == 0:
+        return z
+    if noise is not None:
+        noise = _dev_f32(noise, moments.device)
+        if tuple(noise.shape) != tuple(z.shape):
+            raise ValueError(f"noise of shape {tuple(noise.shape)} for a posterior of shape {tuple(z.shape)}")
+    _chk(lib().df_posterior_sample(_ptr(moments), _ptr(noise) if noise is not None else None, _ptr(z), B, c2 // 2, H * W,
+                                   float(scale), _stream()))
+    return z
 
 
 def q_sample_blend(img, x0, noise, mask, sqrt_acp, sqrt_one_minus_acp):

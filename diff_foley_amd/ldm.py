@@ -145,7 +145,8 @@ class _DiffusionWrapperFacade(_Facade):
 
 
 class _FirstStageFacade(_Facade):
-    """AutoencoderKL.decode(z) (autoencoder.py: post_quant_conv -> decoder), i.e. decode_first_stage without its 1/scale_factor."""
+    """AutoencoderKL.decode(z) (autoencoder.py: post_quant_conv -> decoder), i.e. decode_first_stage without its 1/scale_factor, and
+    AutoencoderKL.encode(x) when the checkpoint's encoder + quant_conv were loaded."""
     _what = "first_stage_model"
 
     def decode(self, z):
@@ -154,7 +155,51 @@ class _FirstStageFacade(_Facade):
         return m.decode_first_stage(zs)
 
     def encode(self, x):
-        raise NotImplementedError("the VAE encoder is not on the sampling path (only post_quant_conv + decoder are loaded)")
+        """AutoencoderKL.encode (autoencoder.py:324-328): the posterior over the latent of a mel image x [B][in_channels][H][W]."""
+        return self._m.encode_first_stage(x)
+
+
+class DiagonalGaussianDistribution:
+    """The posterior ``first_stage_model.encode`` returns (stage1_autoencoder/model.py:34-72): same attributes and methods, the
+    tensors live on the engine's device.  ``parameters`` [B][2 zc][h][w] comes from df_vae_encode; ``sample`` runs df_posterior_sample;
+    ``kl`` / ``nll`` (training-time losses, not on any hot path) are torch expressions on the device tensors."""
+
+    def __init__(self, parameters, deterministic=False):
+        self.parameters = parameters
+        self.mean, logvar = torch.chunk(parameters, 2, dim=1)
+        self.logvar = torch.clamp(logvar, -30.0, 20.0)
+        self.deterministic = deterministic
+        if deterministic:
+            self.var = self.std = torch.zeros_like(self.mean)
+        else:
+            self.std = torch.exp(0.5 * self.logvar)
+            self.var = torch.exp(self.logvar)
+
+    def sample(self, scale=1.0):
+        """mean + std * randn (model.py:45-47), times ``scale`` (not a reference argument: get_first_stage_encoding folds its
+        scale_factor into the same launch).  The noise is drawn like the reference draws it -- torch.randn(shape) from the CPU default
+        generator, then uploaded -- so torch.manual_seed(s) gives the reference's sample."""
+        if self.deterministic:
+            return E.posterior_sample(self.parameters, None, scale)
+        noise = torch.randn(self.mean.shape).to(device=self.parameters.device)
+        return E.posterior_sample(self.parameters, noise, scale)
+
+    def kl(self, other=None):
+        if self.deterministic:
+            return torch.Tensor([0.])
+        if other is None:
+            return 0.5 * torch.sum(torch.pow(self.mean, 2) + self.var - 1.0 - self.logvar, dim=[1, 2, 3])
+        return 0.5 * torch.sum(torch.pow(self.mean - other.mean, 2) / other.var + self.var / other.var - 1.0 - self.logvar
+                               + other.logvar, dim=[1, 2, 3])
+
+    def nll(self, sample, dims=[1, 2, 3]):
+        if self.deterministic:
+            return torch.Tensor([0.])
+        import math
+        return 0.5 * torch.sum(math.log(2.0 * math.pi) + self.logvar + torch.pow(sample - self.mean, 2) / self.var, dim=dims)
+
+    def mode(self):
+        return self.mean
 
 
 class _CondStageFacade(_Facade):
@@ -197,7 +242,9 @@ class LatentDiffusion:
                                           f"(built for {k}={v!r})")
         self.vae_cfg = dict(z_channels=dd["z_channels"], embed_dim=fs["embed_dim"], ch=dd["ch"],
                             ch_mult=[int(v) for v in dd["ch_mult"]], num_res_blocks=dd["num_res_blocks"],
-                            out_ch=dd["out_ch"])
+                            out_ch=dd["out_ch"], in_channels=int(dd.get("in_channels", 3)))
+        self._double_z = bool(dd.get("double_z", True))
+        self._has_encoder = False
         self.cond_cfg = {k: _params(cond_stage_config)[k] for k in ("origin_dim", "embed_dim", "seq_len")}
         self.channels = channels
         self.image_size = image_size
@@ -226,11 +273,22 @@ class LatentDiffusion:
                 "cond_stage_model.")
         self._state = {k: v for k, v in state_dict.items() if k.startswith(need)}
         from . import synth
-        _check_shapes(self._state, synth.state_dict_spec(self.unet_cfg, self.vae_cfg, self.cond_cfg), "LatentDiffusion")
+        # The VAE encoder + quant_conv (first_stage_model.encode) are taken only as the COMPLETE key set of the configured
+        # architecture; any partial set stays out and is reported as unexpected, as every encoder key was before the encoder existed.
+        enc_spec = synth.vae_encoder_spec(self.vae_cfg, "first_stage_model.")
+        self._has_encoder = all(k in state_dict for k in enc_spec)
+        if self._has_encoder:
+            if not self._double_z:
+                raise NotImplementedError("first_stage_config.ddconfig: double_z=False is not supported by libdfengine (the posterior "
+                                          "needs mean and logvar)")
+            self._state.update({k: state_dict[k] for k in enc_spec})
+        _check_shapes(self._state, synth.state_dict_spec(self.unet_cfg, self.vae_cfg, self.cond_cfg, with_encoder=self._has_encoder),
+                      "LatentDiffusion")
         for k in BUFFER_NAMES:            # checkpoints carry the schedule buffers too
             if k in state_dict:
                 setattr(self, k, state_dict[k].detach().float().cpu())
-        unexpected = [k for k in state_dict if not k.startswith(need) and k not in BUFFER_NAMES]
+        unexpected = [k for k in state_dict if not k.startswith(need) and k not in BUFFER_NAMES
+                      and not (self._has_encoder and k in enc_spec)]
         if strict and unexpected:
             raise RuntimeError(f"unexpected keys: {unexpected[:5]} ...")
         if self.engine is not None:
@@ -319,6 +377,8 @@ class LatentDiffusion:
         eng.config_unet(self.unet_cfg)
         eng.config_vae(self.vae_cfg, self.scale_factor)
         eng.config_cond(self.cond_cfg)
+        eng.config_vae_encoder(dict(in_channels=self.vae_cfg["in_channels"]) if self._has_encoder else None)
+        eng.vae_embed_dim = self.vae_cfg["embed_dim"]
         eng.cond_embed_dim = self.cond_cfg["embed_dim"]
         eng.cond_origin_dim = self.cond_cfg["origin_dim"]
         eng.unet_context_dim = self.unet_cfg["context_dim"]
@@ -340,6 +400,8 @@ class LatentDiffusion:
         if self.engine is None:
             raise RuntimeError("load_packed: call .cuda(device) first")
         self._configure()
+        self._has_encoder = False         # the packed blob does not carry the VAE encoder: encode raises on an importing rank
+        self.engine.config_vae_encoder(None)
         self.engine.import_packed(manifest, blob)
         self.engine.finalize()
         self._state = {}      # (no range probe here: the exporting rank ran it on these very weights)
@@ -415,6 +477,30 @@ class LatentDiffusion:
             raise NotImplementedError("VQ code-book decoding is not on the path (AutoencoderKL first stage)")
         # any batch size: df_vae_decode slices batches above 16 samples itself (2 GiB operand addressing, include/df_engine.h)
         return self._require().vae_decode(z)
+
+    @_locked
+    @torch.no_grad()
+    def encode_first_stage(self, x):
+        """ddpm.py:860-899 without split_input_params: first_stage_model.encode(x), the posterior of the mel image x
+        [B][in_channels][H][W] (H, W multiples of the encoder's downsampling).  Needs the checkpoint's first_stage_model.encoder.* and
+        quant_conv.* tensors: without them (a sampling-only state dict, a rank that imported the packed blob) it raises."""
+        if not self._has_encoder:
+            raise NotImplementedError("the VAE encoder is not loaded: load_state_dict was given no complete set of "
+                                      "first_stage_model.encoder.* / first_stage_model.quant_conv.* tensors")
+        return DiagonalGaussianDistribution(self._require().vae_encode(x))
+
+    @_locked
+    @torch.no_grad()
+    def get_first_stage_encoding(self, encoder_posterior):
+        """ddpm.py:559-566: scale_factor * posterior.sample() (one launch, the scale folded in), or scale_factor * tensor.  The
+        reference's isinstance check names the class of models/distribution.py while its autoencoder returns the one of
+        stage1_autoencoder/model.py, so it raises on its own posterior; this facade accepts the posterior its encode returns."""
+        if isinstance(encoder_posterior, DiagonalGaussianDistribution):
+            return encoder_posterior.sample(scale=float(self.scale_factor))
+        if isinstance(encoder_posterior, torch.Tensor):
+            self._require()
+            return E.lincomb([(float(self.scale_factor), E._dev_f32(encoder_posterior, self.device))])
+        raise NotImplementedError(f"encoder_posterior of type '{type(encoder_posterior)}' not yet implemented")
 
     @_locked
     @torch.no_grad()

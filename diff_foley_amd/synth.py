@@ -10,7 +10,7 @@ can be regenerated bit-identically anywhere without being stored.
 ``LatentDiffusion.state_dict()`` has for the sub-modules on the hot path
 (SURVEY.md section 5 "Checkpoint"): ``model.diffusion_model.*``,
 ``first_stage_model.{post_quant_conv,decoder}.*``, ``cond_stage_model.*`` and the
-classifier's ``model.*``.  tests/golden/make_golden.py asserts that names and shapes
+classifier's ``model.*``; optionally ``first_stage_model.{encoder,quant_conv}.*``.  tests/golden/make_golden.py asserts that names and shapes
 agree with the real reference modules.
 """
 import zlib
@@ -161,6 +161,32 @@ def vae_decoder_spec(cfg, prefix=""):
     return spec
 
 
+def vae_encoder_spec(cfg, prefix=""):
+    """Encoder + quant_conv key layout (stage1_autoencoder/model.py:463-527, autoencoder.py:303): what
+    ``first_stage_model.encode`` needs.  ``cfg["in_channels"]`` (default 3, Stage2_LDM.yaml:47) is the image's channel count."""
+    spec = OrderedDict()
+    ch, mult, nrb = cfg["ch"], cfg["ch_mult"], cfg["num_res_blocks"]
+    e = prefix + "encoder."
+    _conv(spec, e + "conv_in", cfg.get("in_channels", 3), ch, 3)
+    bi = ch
+    for lvl in range(len(mult)):
+        bo = ch * mult[lvl]
+        for ib in range(nrb):
+            _vae_res(spec, e + f"down.{lvl}.block.{ib}", bi, bo)
+            bi = bo
+        if lvl != len(mult) - 1:
+            _conv(spec, e + f"down.{lvl}.downsample.conv", bi, bi, 3)
+    _vae_res(spec, e + "mid.block_1", bi, bi)
+    _norm(spec, e + "mid.attn_1.norm", bi)
+    for n in ("q", "k", "v", "proj_out"):
+        _conv(spec, e + "mid.attn_1." + n, bi, bi, 1)
+    _vae_res(spec, e + "mid.block_2", bi, bi)
+    _norm(spec, e + "norm_out", bi)
+    _conv(spec, e + "conv_out", bi, 2 * cfg["z_channels"], 3)
+    _conv(spec, prefix + "quant_conv", 2 * cfg["z_channels"], 2 * cfg["embed_dim"], 1)
+    return spec
+
+
 def cond_spec(cfg, prefix=""):
     spec = OrderedDict()
     _lin(spec, prefix + "embedder.0", cfg["origin_dim"], cfg["embed_dim"])
@@ -168,11 +194,14 @@ def cond_spec(cfg, prefix=""):
     return spec
 
 
-def state_dict_spec(unet=UNET_FULL, vae=VAE_FULL, cond=COND_FULL):
-    """(name -> shape) for the LatentDiffusion sub-modules on the hot path."""
+def state_dict_spec(unet=UNET_FULL, vae=VAE_FULL, cond=COND_FULL, with_encoder=False):
+    """(name -> shape) for the LatentDiffusion sub-modules on the hot path; ``with_encoder`` adds the VAE encoder + quant_conv
+    (``first_stage_model.encode``: inpainting / continuation callers)."""
     spec = OrderedDict()
     spec.update(unet_spec(unet, "model.diffusion_model."))
     spec.update(vae_decoder_spec(vae, "first_stage_model."))
+    if with_encoder:
+        spec.update(vae_encoder_spec(vae, "first_stage_model."))
     spec.update(cond_spec(cond, "cond_stage_model."))
     return spec
 

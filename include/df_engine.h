@@ -48,6 +48,12 @@ typedef struct {
   float scale_factor;
 } df_vae_config;
 
+/* What AutoencoderKL's Encoder needs beyond the decoder's df_vae_config -- stage1_autoencoder/model.py:463-527, Stage2_LDM.yaml:47: the channels of
+ * the image it reads.  ch, ch_mult, num_res_blocks, z_channels and embed_dim are the decoder's (double_z = true). */
+typedef struct {
+  int in_channels;
+} df_vae_encoder_config;
+
 /* Video_Feat_Encoder_Posembed (Stage2_LDM.yaml:62-67). */
 typedef struct {
   int origin_dim, embed_dim, seq_len;
@@ -78,6 +84,10 @@ const char* df_operand_dtype(void);
 int df_config_unet(df_ctx* ctx, const df_unet_config* cfg);
 int df_config_vae(df_ctx* ctx, const df_vae_config* cfg);
 int df_config_cond(df_ctx* ctx, const df_cond_config* cfg);
+/* Optional: the VAE encoder + quant_conv ("first_stage_model.encoder.*", "first_stage_model.quant_conv.*"; autoencoder.py:324-328).
+ * Configured only by a caller that loads those tensors: df_finalize then requires every one of them.  cfg == NULL takes the encoder
+ * out of the configuration again.  in_channels above 4 is refused when a plan is built. */
+int df_config_vae_encoder(df_ctx* ctx, const df_vae_encoder_config* cfg);
 int df_config_classifier(df_ctx* ctx, const df_unet_config* cfg);
 /* Tensors of the CAVP video branch are loaded under "cavp." + the CAVP_Inference state_dict key
  * ("cavp.video_encoder.conv1.conv.weight", "cavp.video_encoder.layer1.0.conv1.bn.running_var",
@@ -138,6 +148,19 @@ int df_unet_forward_cfg_ts(df_ctx* ctx, const float* x_dev, int ts_index, float*
  * z [B][z_channels][H][W] fp32 -> out [B][out_ch][H*2^(n_mult-1)][W*2^(n_mult-1)] fp32.  Any B: batches whose widest
  * activation would exceed the 2 GiB operand addressing (B > 16 at the full decoder) run as slices inside this call. */
 int df_vae_decode(df_ctx* ctx, const float* z_dev, float* out_dev, int B, int H, int W, void* stream);
+
+/* ---- AutoencoderKL.encode up to the posterior's parameters (autoencoder.py:324-328 -> stage1_autoencoder/model.py:529-554, the
+ * Downsample of :167-171), as LatentDiffusion.encode_first_stage reaches it (ddpm.py:860-899 without split_input_params).
+ * x [B][in_channels][H][W] fp32 -> moments [B][2*embed_dim][H/f][W/f] fp32 = quant_conv(encoder(x)), f = 2^(n_mult-1): the
+ * `parameters` of the DiagonalGaussianDistribution (model.py:34-37), mean in the first embed_dim channels, logvar in the rest.
+ * H and W must be positive multiples of f (the reference floors odd maps; this engine refuses them).  Any B: batches whose widest
+ * operand would pass the 2 GiB operand addressing run as slices inside this call, like df_vae_decode. */
+int df_vae_encode(df_ctx* ctx, const float* x_dev, float* moments_dev, int B, int H, int W, void* stream);
+/* DiagonalGaussianDistribution.sample() (model.py:38-47) with LatentDiffusion.get_first_stage_encoding's scale_factor (ddpm.py:559-566)
+ * folded in: z = scale * (mean + exp(0.5 * clamp(logvar, -30, 20)) * noise); moments [B][2*zc][HW], noise / z [B][zc][HW] fp32.
+ * noise_dev may be NULL: z = scale * mean (mode(), model.py:71-72).  Stateless, like df_lincomb. */
+int df_posterior_sample(const float* moments_dev, const float* noise_dev, float* z_dev, int B, int zc, int HW, float scale,
+                        void* stream);
 
 /* ---- Alignment classifier forward (alignment_classifier.py:269-271 -> alignment_backbone.py:656-686)
  * x [B][C][H][W], t [B], video_feat [B][T][context_dim] (raw CAVP features) -> prob [B][out_channels] */
@@ -268,6 +291,26 @@ int df_test_geglu(const uint16_t* A_dev, const uint16_t* W_dev, const void* stat
                   uint16_t* out_dev, int M, int K, int N1, int tile, int dbg, void* stream);
 int df_test_conv3x3_fewout(const uint16_t* A_nhwc_dev, const uint16_t* W_okki_dev, const float* bias_dev, float* out_nchw_dev, int NB,
                            int H, int W, int Cin, int Cout /* <= 4 */, void* stream);
+/* The VAE encoder's conv_in kernel alone (csrc/elementwise.hip conv3x3_fewin; model.py:479-483): x NCHW fp32 [NB][Cin <= 4][H][W],
+ * W OIHW fp32, out fp32 rows [NB*H*W][ldo >= Cout]. */
+int df_test_conv3x3_fewin(const float* x_nchw_dev, const float* W_oihw_dev, const float* bias_dev, float* out_dev, int ldo, int NB,
+                          int H, int W, int Cin, int Cout, void* stream);
+/* The same conv through the route the dedicated kernel replaces (tools/vae_encode_bench.py): pack to 64 operand-type channels
+ * (xpad [NB*H*W][64], wpad [Cout][9][64] scratch), then the implicit GEMM on the builder's own tile choice. */
+int df_test_conv3x3_fewin_gemm(const float* x_nchw_dev, const float* W_oihw_dev, const float* bias_dev, float* out_dev,
+                               uint16_t* xpad_dev, uint16_t* wpad_dev, int NB, int H, int W, int Cin, int Cout, void* stream);
+/* df_vae_encode of B samples with ONE intermediate tensor copied out as it is produced (tests: the hooked stages of the reference's
+ * Encoder.forward, model.py:529-554): tap 0 = conv_in's output, tap 1 + l = the Downsample output of level l, tap 100 = mid.block_2's
+ * output; tap_out fp32 NHWC rows [B*h*w][C] of that stage.  A plan of its own per tap (the copy stands between a GEMM and the GroupNorm
+ * that otherwise takes over its split-K reduce: same arithmetic, possibly another summation order); B within one slice of df_vae_encode. */
+int df_test_vae_encode_tap(df_ctx* ctx, const float* x_dev, float* moments_dev, float* tap_out_dev, int tap, int B, int H, int W,
+                           void* stream);
+/* Stride-2 3x3 conv with GemmParams::pad = pad: 1 = the symmetric Downsample of the UNet (df_test_conv3x3 with stride 2), 0 = the VAE
+ * encoder's F.pad(x, (0,1,0,1)) + padding-0 conv (model.py:167-171).  A [NB][H][W][Cin] and W [Cout][3][3][Cin] operand type, C fp32
+ * [NB*(H/2)*(W/2)][Cout].  _valid: 1 when gemm_route accepts (tile, splitk) for this problem, else 0 (host only). */
+int df_test_conv3x3_down(const uint16_t* A_dev, const uint16_t* W_dev, const float* bias_dev, float* C_dev, int NB, int H, int W,
+                         int Cin, int Cout, int pad, int tile, int splitk, void* stream);
+int df_test_conv3x3_down_valid(int NB, int H, int W, int Cin, int Cout, int pad, int tile, int splitk);
 int df_test_gemm_epi(const uint16_t* A_dev, const uint16_t* W_dev, const float* bias_dev, const float* res_dev, void* C_dev,
                      int M, int N, int K, int act /*0 none, 1 SiLU, 2 ReLU*/, int out_operand, int tile, int splitk,
                      void* stream);
