@@ -165,7 +165,12 @@ int df_finalize(df_ctx* c) {
   });
 }
 
-int df_autotune(df_ctx* c, int enable) { return guard([&] { c->autotune = enable != 0; }); }
+int df_autotune(df_ctx* c, int enable) {
+  return guard([&] {
+    if (enable && c->poison_on) fail("df_autotune: df_debug_poison is on (the tuner re-runs ops out of plan order, which poisoned workspaces do not survive)");
+    c->autotune = enable != 0;
+  });
+}
 
 int df_cavp_encode(df_ctx* c, const float* video, float* out, int B, int T, int H, int W, int normalize, void* stream) {
   return guard([&] {
@@ -606,6 +611,7 @@ int df_plan_count(df_ctx* c, int64_t* n_plans, int64_t* workspace_bytes) {
     int64_t b = 0;
     for (auto& kv : c->plans) {
       for (auto& blk : kv.second->owned) b += (int64_t)blk.bytes;
+      for (auto& blk : kv.second->pinned) b += (int64_t)blk.bytes;
       b += (int64_t)kv.second->partial_bytes;
     }
     *workspace_bytes = b;
@@ -712,6 +718,23 @@ int df_debug_requant(df_ctx* c, const char* prefixes) {
       if (e > pos) c->rq_prefix.push_back(t.substr(pos, e - pos));
       pos = e + 1;
     }
+  });
+}
+
+// Plan workspaces are built poisoned and re-poisoned at every release (Plan::poison, run_ops).  What Plan::alloc does at build time
+// changes with the switch, so the cached plans go, as they do after a weight reload.
+int df_debug_poison(df_ctx* c, int enable) {
+  return guard([&] {
+    const bool on = enable != 0;
+    if (on && c->autotune)
+      fail("df_debug_poison: df_autotune is on (the tuner re-runs ops out of plan order, which poisoned workspaces do not survive): "
+           "call df_autotune(ctx, 0) first");
+    if (on == c->poison_on) return;
+    HIPCHK(hipDeviceSynchronize());       // the plans' buffers may still be read by queued launches
+    c->plans.clear();
+    c->plan_tick.clear();
+    c->last_unet = nullptr;
+    c->poison_on = on;
   });
 }
 

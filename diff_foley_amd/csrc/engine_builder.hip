@@ -49,11 +49,13 @@ void Builder::forget_pend() {
 }
 
 void Builder::other(const char* tag, std::function<hipError_t(hipStream_t, const RunArgs&)> fn) {
-  forget_pend();
   Op o;
   o.fn = std::move(fn);
   o.tag = tag;
   pl->ops.push_back(std::move(o));
+  // behind the push, as in gemm(): a held residual is read by THIS op when it is the GroupNorm that claimed the pending GEMM, so its
+  // postponed release takes effect behind the op (the index df_debug_poison fills it at), not in front of it
+  forget_pend();
 }
 
 void Builder::emits(const bf16_t* p, long rows, int cols, int ld) {

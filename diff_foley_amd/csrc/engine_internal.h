@@ -109,6 +109,13 @@ struct Plan {
   std::vector<Op> ops;
   std::vector<Block> owned;      // every hipMalloc'd block (freed with the plan)
   std::vector<Block> freelist;   // build-time reuse
+  std::vector<Block> pinned;     // alloc_zeroed / alloc_index blocks: never recycled, never poisoned (freed with the plan)
+  // debug (df_debug_poison): fresh blocks are filled with 0xFF bytes (NaN as fp32 / bf16 / fp16) instead of zeros, and every
+  // release is recorded as (ops.size() when it took effect, block): run_ops fills the block again right behind the op in front of
+  // that index.  An op that reads what no earlier op of the same run wrote -- build-time zeros, a previous tenant's bytes, its own
+  // buffer after the release -- then reads NaN.
+  bool poison = false;
+  std::vector<std::pair<size_t, Block>> poison_at;      // sorted by op index in finish_plan
   float* partial = nullptr;      // shared split-K scratch
   size_t partial_bytes = 0;
   double gemm_flops = 0, weight_bytes = 0;
@@ -141,6 +148,7 @@ struct Plan {
   int chk_n = 0;
   ~Plan() {
     for (auto& b : owned) (void)hipFree(b.p);
+    for (auto& b : pinned) (void)hipFree(b.p);
     if (partial) (void)hipFree(partial);
     if (chk_list) (void)hipFree(chk_list);
     if (Etab) (void)hipFree(Etab);
@@ -160,10 +168,24 @@ struct Plan {
     }
     void* p = nullptr;
     HIPCHK(hipMalloc(&p, bytes));
-    HIPCHK(hipMemset(p, 0, bytes));
+    HIPCHK(hipMemset(p, poison ? 0xFF : 0, bytes));
     owned.push_back({p, bytes});
     return p;
   }
+  // A block of zeros that stays what it is: zeroed here, never on the freelist (release() does not know it), never poisoned.  For
+  // regions an op reads but no op ever writes -- the pad columns behind the columns a GEMM stores.  The ops that write INTO such a
+  // block write the same elements in every run, so the zeros around them are the build's in every run.
+  void* alloc_zeroed(size_t bytes) {
+    bytes = (bytes + 255) & ~(size_t)255;
+    void* p = nullptr;
+    HIPCHK(hipMalloc(&p, bytes));
+    HIPCHK(hipMemset(p, 0, bytes));
+    pinned.push_back({p, bytes});
+    return p;
+  }
+  // A block whose content is read as an integer, an index or a pointer: pinned and zeroed like alloc_zeroed, and named apart so that
+  // the poison pattern can never become an address (no plan builder needs one today)
+  void* alloc_index(size_t bytes) { return alloc_zeroed(bytes); }
   // One buffer may be HELD: a release() of it is postponed until unhold() (Builder: the fp32 residual of a GEMM whose split-K
   // reduce is handed to the next op must not be recycled for that op's own outputs).
   const void* held = nullptr;
@@ -184,6 +206,7 @@ struct Plan {
     for (auto& b : owned)
       if (b.p == p) {
         freelist.push_back(b);
+        if (poison) poison_at.push_back({ops.size(), b});
         return;
       }
   }
@@ -223,6 +246,7 @@ struct __attribute__((visibility("hidden"))) df_ctx {
   float* ctx_copy = nullptr;
   size_t ctx_copy_bytes = 0;
   bool autotune = false;
+  bool poison_on = false;         // df_debug_poison: plans are built with Plan::poison (switching it drops the cached plans)
   bool reloaded = false;          // a tensor that already existed was loaded again: packed operand copies are stale
   bool prof_on = false;
   std::vector<hipEvent_t> prof_ev;      // pairs (start, stop) per executed op while profiling

@@ -1,5 +1,5 @@
-// libdfengine: plan execution -- finish_plan, the launch loop run_ops with its three debug hooks (checksums, saturation counts,
-// bf16 re-rounding), and the plan cache get_plan (types: engine_internal.h).
+// libdfengine: plan execution -- finish_plan, the launch loop run_ops with its four debug hooks (checksums, saturation counts,
+// bf16 re-rounding, workspace poisoning), and the plan cache get_plan (types: engine_internal.h).
 #include "engine_internal.h"
 
 DFE_NAMESPACE {
@@ -10,6 +10,8 @@ void finish_plan(df_ctx* c, Plan* pl) {
     for (auto& o : pl->ops)
       if (o.is_gemm && o.gp.splitk > 1) o.gp.partial = pl->partial;
   }
+  std::stable_sort(pl->poison_at.begin(), pl->poison_at.end(),
+                   [](const std::pair<size_t, Block>& a, const std::pair<size_t, Block>& b) { return a.first < b.first; });
   HIPCHK(hipStreamSynchronize(c->pack_stream));   // weight packing done before first use
 }
 
@@ -39,6 +41,7 @@ void checksum_after_op(df_ctx* c, Plan* pl, size_t op_index, hipStream_t s) {
   if (!pl->chk_list) {
     std::vector<ChkBuf> v;
     for (auto& b : pl->owned) v.push_back({(const uint32_t*)b.p, (unsigned long long)(b.bytes / 4)});
+    for (auto& b : pl->pinned) v.push_back({(const uint32_t*)b.p, (unsigned long long)(b.bytes / 4)});
     if (pl->partial) v.push_back({(const uint32_t*)pl->partial, (unsigned long long)(pl->partial_bytes / 4)});
     pl->chk_n = (int)v.size();
     if (!v.empty()) {
@@ -141,6 +144,22 @@ void requant_after_op(df_ctx* c, Plan* pl, size_t op_index, hipStream_t s) {
   }
 }
 
+// df_debug_poison: the blocks whose release took effect right behind op `op_index` are filled with 0xFF bytes -- whoever reads them
+// from here on without writing first (the next tenant, or the owner that released too early) reads NaN
+void poison_after_op(Plan* pl, size_t op_index, hipStream_t s) {
+  auto it = std::lower_bound(pl->poison_at.begin(), pl->poison_at.end(), op_index + 1,
+                             [](const std::pair<size_t, Block>& e, size_t v) { return e.first < v; });
+  for (; it != pl->poison_at.end() && it->first == op_index + 1; ++it) HIPCHK(hipMemsetAsync(it->second.p, 0xFF, it->second.bytes, s));
+}
+
+// ... and the slabs a split-K GEMM may use, in front of its launch: an element that no K slice writes and the reduce (or the
+// GroupNorm the reduce was handed to) still sums is NaN
+void poison_partial(Plan* pl, const GemmParams& g, hipStream_t s) {
+  if (!pl->partial || g.partial != pl->partial) return;
+  const size_t need = (size_t)g.splitk * g.M * g.N * 4 * (g.taps == 4 ? 4 : 1);
+  HIPCHK(hipMemsetAsync(pl->partial, 0xFF, std::min(need, pl->partial_bytes), s));
+}
+
 }  // namespace
 
 void run_ops(df_ctx* c, Plan* pl, size_t begin, size_t end, hipStream_t s, const RunArgs& a) {
@@ -164,6 +183,7 @@ void run_ops(df_ctx* c, Plan* pl, size_t begin, size_t end, hipStream_t s, const
       if (o.c_ext) g.C = a.out;
       if (o.cfg_ext && g.splitk > 1) { g.cfg_out = a.out; g.cfg_scale = a.scale; }
       if (o.defer && g.splitk > 1) g.defer_reduce = 1;
+      if (pl->poison && g.splitk > 1) poison_partial(pl, g, s);
       e = launch_gemm(g, o.tile, o.batch, s, &why);
     } else {
       e = o.fn(s, a);
@@ -180,6 +200,7 @@ void run_ops(df_ctx* c, Plan* pl, size_t begin, size_t end, hipStream_t s, const
       c->prof_op.push_back(&o);
       c->prof_used += 2;
     }
+    if (pl->poison) poison_after_op(pl, i, s);
     if (!c->rq_prefix.empty()) requant_after_op(c, pl, i, s);
     if (c->chk_on) checksum_after_op(c, pl, i, s);
     if (c->sat_on) saturations_after_op(c, pl, i, s);
@@ -210,6 +231,7 @@ Plan* get_plan(df_ctx* c, const std::string& key, const std::function<void(Plan*
     c->plans.erase(victim);
   }
   std::unique_ptr<Plan> p(new Plan());
+  p->poison = c->poison_on;
   build(p.get());
   const bool tunable = !p->fixed_choices;
   if (tunable && (c->autotune || g_tune_imported)) {

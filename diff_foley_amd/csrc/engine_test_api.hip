@@ -425,6 +425,7 @@ int df_test_unet_block(df_ctx* c, const char* prefix, int kind, const float* x, 
     const df_unet_config& u = c->ucfg;
     const std::string pre = "model.diffusion_model.", p = prefix;
     Plan plan;
+    plan.poison = c->poison_on;
     Builder b{c, &plan, pre, 0};
     const int rows = N * H * W, temb = 4 * u.model_channels;
     F32 xin{b.buf<float>((size_t)rows * Cin), rows, Cin, Cin};
@@ -466,6 +467,47 @@ int df_test_unet_block(df_ctx* c, const char* prefix, int kind, const float* x, 
     RunArgs a;
     run_ops(c, &plan, 0, plan.ops.size(), s, a);
     HIPCHK(hipMemcpyAsync(out, dst.p, (size_t)orow * Cout * 4, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));
+  });
+}
+
+// df_debug_poison checked against plans with a planted defect (include/df_engine.h): only Plan::alloc / release and the
+// element-wise launchers, every access inside the plan's own blocks.
+int df_test_poison_selftest(df_ctx* c, int defect, float* out_dev, void* stream) {
+  return guard([&] {
+    if (defect < 0 || defect > 2) fail("df_test_poison_selftest: defect %d (0 .. 2)", defect);
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    constexpr int n = 1024, h = n / 2;
+    Plan plan;
+    plan.poison = c->poison_on;
+    Builder b{c, &plan, "", 0};
+    float* x = b.buf<float>(n);
+    {
+      std::vector<float> xh(n);
+      for (int i = 0; i < n; ++i) xh[i] = (float)(i % 37 - 18) / 8.f;
+      HIPCHK(hipMemcpy(x, xh.data(), n * sizeof(float), hipMemcpyHostToDevice));
+    }
+    auto lincomb = [&](const char* tag, float* out, const float* in0, float c0, const float* in1, float c1, long cnt) {
+      b.other(tag, [=](hipStream_t st, const RunArgs&) {
+        const float* in[2] = {in0, in1};
+        const float coef[2] = {c0, c1};
+        return launch_lincomb(out, in, coef, in1 ? 2 : 1, cnt, st);
+      });
+    };
+    float* A = b.buf<float>(n);
+    lincomb("self.a", A, x, 2.f, nullptr, 0.f, n);
+    float* B = b.buf<float>(n);
+    lincomb("self.b", B, A, 1.f, x, 1.f, n);
+    plan.release(A);
+    float* Cc = b.buf<float>(h);      // the freelist hands out A's block: n floats for a tenant of h
+    if (Cc != A) fail("df_test_poison_selftest: the freelist did not recycle the released block");
+    lincomb("self.c", Cc, B, 0.5f, defect == 2 ? Cc + h : nullptr, 1.f, h);
+    float* o = b.buf<float>(h);
+    lincomb("self.out", o, Cc, 1.f, defect == 1 ? A + h : B + h, 1.f, h);
+    finish_plan(c, &plan);
+    run_ops(c, &plan, 0, plan.ops.size(), s, RunArgs{});
+    HIPCHK(hipMemcpyAsync(out_dev, o, h * sizeof(float), hipMemcpyDeviceToDevice, s));
     HIPCHK(hipStreamSynchronize(s));
   });
 }

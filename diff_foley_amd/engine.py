@@ -162,6 +162,8 @@ _SIGS = {
     "df_debug_saturations_read": [C.c_void_p, C.POINTER(C.c_uint64), C.c_int64, C.POINTER(C.c_int64)],
     "df_debug_saturation_label": [C.c_void_p, C.c_int64, C.c_char_p, C.c_int64],
     "df_debug_requant": [C.c_void_p, C.c_char_p],
+    "df_debug_poison": [C.c_void_p, C.c_int],
+    "df_test_poison_selftest": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
     "df_test_gemm_epi": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                          C.c_int, C.c_int, C.c_int, C.c_void_p],
     "df_test_gemm_dual": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -730,6 +732,17 @@ class Engine:
             _chk(self.L.df_debug_saturation_label(self._h, i, buf, 200), self.L)
             res.append((buf.value.decode(), int(out[i])))
         return res
+
+    def debug_poison(self, enable):
+        """Debug: build plan workspaces poisoned (0xFF bytes = NaN) and poison every block again where its plan releases it, so that an
+        op which reads what its plan did not write in the same run produces NaN (include/df_engine.h).  Drops the cached plans."""
+        _chk(self.L.df_debug_poison(self._h, int(bool(enable))), self.L)
+
+    def poison_selftest(self, defect):
+        """Tests: the four-op plan of df_test_poison_selftest with planted defect 0 (none), 1 or 2 -> its 512 outputs."""
+        out = torch.empty(512, device=self.device, dtype=torch.float32)
+        _chk(self.L.df_test_poison_selftest(self._h, int(defect), _ptr(out), _stream()), self.L)
+        return out
 
     def check_saturations(self):
         """Raises if any op since debug_saturations(True) stored a saturated / non-finite operand value; names the ops."""

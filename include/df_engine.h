@@ -277,6 +277,24 @@ int df_debug_saturations_read(df_ctx* ctx, uint64_t* out, int64_t cap, int64_t* 
  * the op.  The bf16 build accepts the call and changes nothing. */
 int df_debug_requant(df_ctx* ctx, const char* tag_prefixes);
 int df_debug_saturation_label(df_ctx* ctx, int64_t index, char* buf, int64_t len);
+/* Debug: poisoned plan workspaces.  The rule it enforces: an op may read only bytes written earlier in the same run by an op of
+ * its plan, or a pinned zeroed block.  While enabled, (i) a workspace block fresh from the allocator is filled with 0xFF bytes (a NaN as
+ * fp32, bf16 and fp16) instead of zeros, (ii) every block is filled with the pattern again right behind the last op in front of its
+ * release at plan-build time -- whenever that op is among the ops a call executes -- and (iii) the split-K scratch a GEMM may use
+ * (splitk * M * N * 4 bytes, x 4 for the four-phase Upsample conv) is filled in front of every split-K GEMM.  An op that relies on the
+ * build-time zeros, on a previous tenant's bytes or on its own buffer after the release then produces NaN instead of a slightly wrong
+ * number.  The fills are hipMemsetAsync calls on the stream of the run, in op order.  Off (the default), nothing changes.  Switching
+ * drops the context's cached plans (what a block holds when a plan is built changes); refused while df_autotune is on, and
+ * df_autotune(1) is refused while this is on: the tuner re-runs ops out of plan order. */
+int df_debug_poison(df_ctx* ctx, int enable);
+/* Self-test of df_debug_poison (tests/test_plan_poison_gpu.py): a four-op plan of element-wise launches over Plan::alloc / release
+ * blocks, on the fixed input x[i] = ((i % 37) - 18) / 8, i < 1024.  out_dev [512] fp32.
+ *   ops: A = 2 x [1024] ; B = A + x [1024], A released ; C = B / 2 [512], which recycles A's (twice as large) block ;
+ *        out[i] = C[i] + B[512 + i] = 1.5 x[i] + 3 x[512 + i]
+ *   defect 0: that plan.  defect 1 (use after release): the last op reads A[512 + i] for B[512 + i] -- the tail of the block that was
+ *   released behind op 1 and handed to C.  defect 2 (stale tail): op 2 adds C[512 + i], the tail of its oversized recycled block that
+ *   it never wrote, to C[i].  Both defects stay inside A's block, give finite (wrong) numbers with the hook off and NaN with it on. */
+int df_test_poison_selftest(df_ctx* ctx, int defect, float* out_dev, void* stream);
 /* Run ONE op family in isolation for unit tests (see tests/test_kernels_gpu.py). */
 int df_test_scratch_read(void* host, int64_t bytes);     /* the shared scratch of the test entry points (debug stamps) */
 /* df_test_gemm, _gemm_epi, _gemm_dual, df_test_conv3x3, _conv3x3_skip, _conv3x3_ups4 and df_test_geglu are fixed-shape fills of
