@@ -11,7 +11,7 @@ from .ldm import (LatentDiffusion, AlignmentClassifier, CAVPInference, DiagonalG
                   instantiate_from_config)
 from .samplers import DDIMSampler, PLMSSampler, DPMSolverSampler  # noqa: F401
 from .video import ExtractCAVPFeatures, frames_to_tensor  # noqa: F401
-from .vocoder import inverse_op, mel_to_wave  # noqa: F401
+from .vocoder import get_spectrogram, inverse_op, mel_to_wave, wave_to_mel  # noqa: F401
 
 
 def stage2_config(unet=None, vae=None, cond=None):

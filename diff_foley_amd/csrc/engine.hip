@@ -577,6 +577,19 @@ int df_griffinlim(const float* S, const float* phase0, int B, int T, int n_iter,
   });
 }
 
+int df_wave_to_mel(const float* wav, int64_t wav_stride, int B, int L, const float* A, const int32_t* bands, int n_mels,
+                   const float* twiddles, const float* window, float floor, float* mel, void* stream) {
+  return guard([&] {
+    need_positive("wave_to_mel", {{"clips", B}, {"samples", L}, {"mel bins", n_mels}});
+    if (n_mels > 128) fail("wave_to_mel: %d mel bins (the kernel holds at most 128 rows per tile)", n_mels);
+    if (wav_stride < L) fail("wave_to_mel: row stride %ld is shorter than a clip of %d samples", (long)wav_stride, L);
+    if (!wav || !A || !bands || !twiddles || !window || !mel) fail("wave_to_mel: null pointer argument");
+    HIPCHK(launch_wave_to_mel(wav, (long)wav_stride, B, L, A, bands, n_mels, (const float2*)twiddles, window, floor, mel,
+                              (hipStream_t)stream));
+  });
+}
+int df_wave_to_mel_tile(void) { return wave_to_mel_tile(); }
+
 int df_cfg_combine(const float* e2, float* e, int64_t n, float scale, void* stream) {
   return guard([&] { HIPCHK(launch_cfg_combine(e2, e, (long)n, scale, (hipStream_t)stream)); });
 }

@@ -199,3 +199,10 @@ hipError_t launch_mel_to_stft(const float* mel, int B, int NM, int T, const floa
 hipError_t launch_griffinlim(const float* S, const float* phase0, int B, int T, int n_iter, float momentum, const float2* tw,
                              const float* window, const float* wss, float2* angles, float2* reb0, float2* reb1, float* frames,
                              float* y, hipStream_t s);
+// Waveform -> normalised log-mel (TRANSFORMS of data_preprocess/wav2spec.py:145-155): wav [B][wav_stride >= L] fp32 ->
+// out [B][NM][T], T = 1 + L / 256.  A [NM][513] the mel filterbank, bands int32 [NM][2] = (first non-zero bin, count) per row,
+// tw[512] = exp(-2 pi i k/1024), window[1024] periodic hann, floor_v = LowerThresh (1e-5).  One block per tile of
+// wave_to_mel_tile() frames.
+hipError_t launch_wave_to_mel(const float* wav, long wav_stride, int B, int L, const float* A, const int* bands, int NM,
+                              const float2* tw, const float* window, float floor_v, float* out, hipStream_t s);
+int wave_to_mel_tile();

@@ -14,6 +14,29 @@
 //   gl_ifft_kernel      one frame per block: spectrum = S * angles, Hermitian extension, radix-2 FFT in LDS, window.
 //   gl_ola_kernel       window-sum-square normalised overlap-add (gather form: deterministic), centre trimmed.
 //   gl_stft_kernel      reflect-padded frame * window -> FFT -> angle update  a = rebuilt - m/(1+m) * previous; a /= |a|.
+//
+// Waveform -> mel, the forward direction (data_preprocess/wav2spec.py:145-155, 170-189: TRANSFORMS of get_spectrogram, librosa 0.8.0
+// stft + filters.mel at sr 16000, on the CPU there):
+//   wave_to_mel_kernel  one block per tile of WTM_FT consecutive frames of one clip.  The tile's (WTM_FT - 1) * 256 + 1024 samples are
+//                       staged into LDS once (neighbouring frames share 75 % of them; numpy's reflect rule at both clip ends, as in
+//                       gl_stft_kernel), two frames are transformed at a time (512 threads, one half-block per frame), the banded
+//                       Slaney filterbank walks [first_bin, first_bin + count) per mel row from the host's table, the
+//                       tile's mel values wait in LDS, and the log-mel normalisation runs in registers on the way out: rows of WTM_FT
+//                       contiguous floats of out[B][n_mels][T].  No atomics: a pure function of the input.
+//                       Each real frame is ONE 512-point complex FFT of z[n] = x[2n] + i x[2n+1] and a split
+//                       X[k] = E[k] + W^k O[k] (E, O = even / odd part of Z) -- the same halving of the FFT work as packing two
+//                       frames into one 1024-point transform, but every bin of a frame carries only that frame's round-off.
+//                       Packing frames t and t+1 together puts eps * |frame t+1| into frame t's bins: at an onset, where the next
+//                       frame is 100x louder (a burst entering under the window's edge), that is 100x the frame's own error bound
+//                       (tests/test_wave_to_mel_gpu.py judges every element against eps * |its own frame|).
+//                       The epilogue 0.2 * log10(max(floor, mel)) + 0.8 is evaluated in fp64 and rounded once, in the store loop where all
+//                       512 threads share it (131 k logarithms at B = 4, T = 512): fp32 log10f alone costs 0.2 ulp(4) = 5e-8 of output,
+//                       which is 6 ulp of an output of 0.1.
+//                       Tile: WTM_FT = 4 frames, 512 threads.  Measured on an MI355X (tools/wave_to_mel_bench.py, L = 131071, us per call,
+//                       variants alternating in one session): B = 4  17.6 (FT 4) / 21.6 (FT 8) / 37.6 (FT 16); B = 1  13.9 / 20.9 / 37.4;
+//                       B = 64  163.0 / 157.2 / 159.3.  A block is one chain of barriers (nine FFT stages per pair of frames), so a
+//                       larger tile only lengthens it: at B <= 4 no tile gives a CU more than two blocks, so the shortest chain wins, by
+//                       19 % at B = 4; at B = 64 the re-staged samples (1.75x at FT 4, 1.1x at FT 16) cost 4 %.
 #include <algorithm>
 
 #include "common.h"
@@ -222,7 +245,151 @@ __global__ __launch_bounds__(256) void gl_stft_kernel(const float* __restrict__ 
   }
 }
 
+// ---- waveform -> normalised log-mel.  wav [B][wav_stride >= L] ; A [NM][NBIN] ; bands [NM][2] = (first bin, count) ; out [B][NM][T]
+#ifndef WTM_FT
+#define WTM_FT 4                   // frames per block (even); tools/wave_to_mel_bench.py times builds with other values
+#endif
+constexpr int WTM_NT = 512;        // two frames in flight, 256 threads each
+constexpr int WTM_AR = 24;         // filterbank entries of its row a thread keeps in registers (the widest of the 128-row banks: 22)
+constexpr int WTM_NS = (WTM_FT - 1) * HOPV + NFFT, WTM_H = NFFT / 2;
+static_assert(WTM_FT % 2 == 0 && WTM_FT >= 2 && WTM_FT <= 64, "wave_to_mel tile");
+__device__ __forceinline__ int brev9(int i) { return (int)(__brev((unsigned)i) >> 23); }
+
+// radix-2 FFT of 512 complex points held in LDS in bit-reversed order, 256 threads (lt), one butterfly per thread and stage;
+// the twiddle of a length-`len` stage is exp(-2 pi i j / len) = tw[j * (1024 / len)], tw in LDS too: a stage is a barrier and a
+// chain of dependent reads, and a table read from global memory put a cache round trip into every one of the nine.
+// Butterflies written like fft1024's.
+__device__ __forceinline__ void fft512(float2* s, const float2* tw, int lt) {
+#pragma unroll 1
+  for (int len = 2, stride = NFFT / 2; len <= WTM_H; len <<= 1, stride >>= 1) {
+    const int half = len >> 1;
+    __syncthreads();
+    const int j = lt & (half - 1), a = ((lt - j) << 1) + j, b = a + half;
+    const float2 w = tw[j * stride];
+    const float2 u = s[a], v = s[b];
+    float tx = w.x * v.x, ty = w.x * v.y;
+    asm volatile("" : "+v"(tx));
+    asm volatile("" : "+v"(ty));
+    tx = fmaf(-w.y, v.y, tx);
+    ty = fmaf(w.y, v.x, ty);
+    float ax = u.x + tx, ay = u.y + ty, bx = u.x - tx, by = u.y - ty;
+    asm volatile("" : "+v"(ax));
+    asm volatile("" : "+v"(ay));
+    asm volatile("" : "+v"(bx));
+    asm volatile("" : "+v"(by));
+    s[a] = make_float2(ax, ay);
+    s[b] = make_float2(bx, by);
+  }
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(WTM_NT) void wave_to_mel_kernel(const float* __restrict__ wav, long wav_stride, int L, int T, int tiles,
+                                                         const float* __restrict__ A, const int* __restrict__ bands, int NM,
+                                                         const float2* __restrict__ tw, const float* __restrict__ window,
+                                                         float floor_v, float* __restrict__ out) {
+  __shared__ __attribute__((aligned(16))) float xs[WTM_NS];       // the tile's samples, reflect-padded
+  __shared__ float2 s[2][WTM_H];                                  // one 512-point transform per half-block
+  __shared__ float mag[2][FPAD];                                  // |X[0..512]| of the two frames in flight
+  __shared__ float melt[128 * (WTM_FT + 1)];                      // [NM][WTM_FT + 1]: the tile's linear mel
+  __shared__ float2 twl[WTM_H];                                   // the twiddle table
+  const int tid = threadIdx.x, h = tid >> 8, lt = tid & 255;
+  const int b = blockIdx.x / tiles, t0 = (blockIdx.x - b * tiles) * WTM_FT;
+  const float* yb = wav + (long)b * wav_stride;
+  const long P = 2 * ((long)L - 1);                               // np.pad(mode="reflect"): triangular wave of period 2 (L - 1)
+  for (int e = tid; e < WTM_NS; e += WTM_NT) {
+    long i = (long)t0 * HOPV + e - NFFT / 2;
+    if (i < 0 || i >= L) {                                        // both clip ends, more than one reflection for L < 513, L = 1
+      i = P > 0 ? i % P : 0;
+      if (i < 0) i += P;
+      if (i >= L) i = P - i;
+    }
+    xs[e] = yb[i];
+  }
+  for (int e = tid; e < WTM_H; e += WTM_NT) twl[e] = tw[e];
+  // what a thread needs in every pair of frames is read once: its four window values and the head of its filterbank row
+  const float2 wn0 = *reinterpret_cast<const float2*>(&window[2 * lt]), wn1 = *reinterpret_cast<const float2*>(&window[2 * lt + 512]);
+  int k0 = 0, cnt = 0;
+  float ar[WTM_AR];
+  const float* Am = A + (long)min(lt, NM - 1) * NBIN;
+  if (lt < NM) {
+    k0 = min(max(bands[2 * lt], 0), NBIN);
+    cnt = min(max(bands[2 * lt + 1], 0), NBIN - k0);
+  }
+#pragma unroll
+  for (int i = 0; i < WTM_AR; ++i) ar[i] = i < cnt ? Am[k0 + i] : 0.f;
+  __syncthreads();
+#pragma unroll 1
+  for (int f0 = 0; f0 < WTM_FT; f0 += 2) {
+    const int f = f0 + h;
+    const bool live = t0 + f < T;                                 // uniform per half-block (4 wavefronts); barriers stay outside
+    if (live) {
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        const int n = lt + q * 256;
+        const float2 x = *reinterpret_cast<const float2*>(&xs[f * HOPV + 2 * n]);
+        const float2 wn = q ? wn1 : wn0;
+        s[h][brev9(n)] = make_float2(x.x * wn.x, x.y * wn.y);
+      }
+    }
+    fft512(s[h], twl, lt);
+    if (live) {
+      for (int k = lt; k <= WTM_H; k += 256) {                    // X[k] = E[k] + W^k O[k], k = 0..512 ; Z[512] = Z[0]
+        const float2 zk = s[h][k & (WTM_H - 1)], zc = s[h][(WTM_H - k) & (WTM_H - 1)];
+        float ex = 0.5f * (zk.x + zc.x), ey = 0.5f * (zk.y - zc.y);        // E = (Z[k] + conj Z[512-k]) / 2
+        float ox = 0.5f * (zk.y + zc.y), oy = -0.5f * (zk.x - zc.x);       // O = (Z[k] - conj Z[512-k]) / (2i)
+        asm volatile("" : "+v"(ex));
+        asm volatile("" : "+v"(ey));
+        asm volatile("" : "+v"(ox));
+        asm volatile("" : "+v"(oy));
+        float2 w = twl[k & (WTM_H - 1)];
+        if (k == WTM_H) w = make_float2(-1.f, 0.f);               // W^512
+        float tx = w.x * ox, ty = w.x * oy;
+        asm volatile("" : "+v"(tx));
+        asm volatile("" : "+v"(ty));
+        tx = fmaf(-w.y, oy, tx);
+        ty = fmaf(w.y, ox, ty);
+        float xr = ex + tx, xi = ey + ty;
+        asm volatile("" : "+v"(xr));
+        asm volatile("" : "+v"(xi));
+        mag[h][k] = sqrtf(fmaf(xr, xr, xi * xi));
+      }
+    }
+    __syncthreads();
+    if (live && lt < NM) {
+      float acc = 0.f;                                            // ascending k, one fma chain: the order does not depend on WTM_AR
+#pragma unroll
+      for (int i = 0; i < WTM_AR; ++i)
+        if (i < cnt) acc = fmaf(ar[i], mag[h][k0 + i], acc);
+      for (int i = WTM_AR; i < cnt; ++i) acc = fmaf(Am[k0 + i], mag[h][k0 + i], acc);      // wider rows (n_mels < 100): the rest from L2
+      melt[lt * (WTM_FT + 1) + f] = acc;
+    }
+  }
+  __syncthreads();
+  float* ob = out + (long)b * NM * T + t0;
+  for (int e = tid; e < NM * WTM_FT; e += WTM_NT) {
+    const int m = e / WTM_FT, j = e - m * WTM_FT;
+    if (t0 + j < T) {
+      // LowerThresh, Log10, Multiply 20, Subtract 20, Add 100, Divide 100, Clip(0, 1)  =  clip(0.2 log10(max(floor, mel)) + 0.8),
+      // here and not behind each pair of frames: all 512 threads share the logarithms and none sits in a pair's barrier chain
+      const double v = 0.2 * log10((double)fmaxf(floor_v, melt[m * (WTM_FT + 1) + j])) + 0.8;
+      ob[(long)m * T + j] = (float)fmin(fmax(v, 0.0), 1.0);
+    }
+  }
+}
+
 }  // namespace
+
+int wave_to_mel_tile() { return WTM_FT; }
+
+hipError_t launch_wave_to_mel(const float* wav, long wav_stride, int B, int L, const float* A, const int* bands, int NM,
+                              const float2* tw, const float* window, float floor_v, float* out, hipStream_t s) {
+  if (NM > 128 || NM < 1 || B < 1 || L < 1 || wav_stride < L) return hipErrorInvalidValue;
+  const int T = 1 + L / HOPV, tiles = (T + WTM_FT - 1) / WTM_FT;
+  if ((long)B * tiles > 0x7fffffffL) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(wave_to_mel_kernel, dim3(B * tiles), dim3(WTM_NT), 0, s, wav, wav_stride, L, T, tiles, A, bands, NM, tw, window,
+                     floor_v, out);
+  return hipGetLastError();
+}
 
 hipError_t launch_mel_to_stft(const float* mel, int B, int NM, int T, const float* A, const float* At, const float* Pt,
                               float inv_L, int iters, float* S, hipStream_t s) {

@@ -209,6 +209,19 @@ int df_griffinlim(const float* S_dev, const float* phase0_dev, int B, int T, int
                   const float* twiddles_dev, const float* window_dev, const float* wss_dev, float* angles_dev,
                   float* reb0_dev, float* reb1_dev, float* frames_dev, float* wav_dev, void* stream);
 
+/* ---- waveform -> mel, the forward direction of the above (get_spectrogram / TRANSFORMS, data_preprocess/wav2spec.py:145-155,
+ * 170-189; librosa 0.8.0 stft + filters.mel on the CPU there): |stft(y, n_fft 1024, hop 256)| (periodic hann, centred,
+ * np.pad reflect by 512 -- also for clips shorter than the pad) -> mel filterbank -> LowerThresh(floor), Log10, *20, -20, +100,
+ * /100, Clip(0, 1).  wav fp32 [B][wav_stride >= L] -> mel fp32 [B][n_mels][T], T = 1 + L / 256 (the layout encode_first_stage
+ * takes after the channel repeat).  A [n_mels][513] = librosa.filters.mel(sr, 1024, n_mels, fmin, fmax) (sr 16000 in wav2spec.py),
+ * bands int32 [n_mels][2] = (first non-zero bin, count of bins up to the last non-zero one) of every row of A -- the kernel
+ * walks only those; twiddles complex [512] exp(-2 pi i k/1024), window [1024] periodic hann, floor 1e-5.  1 <= n_mels <= 128,
+ * B >= 1, L >= 1; no workspace, no atomics: the result is a pure function of the input.  All pointers device memory, the launch is
+ * asynchronous on `stream`.  df_wave_to_mel_tile: frames per block of this build (returns the count, not a status). */
+int df_wave_to_mel(const float* wav_dev, int64_t wav_stride, int B, int L, const float* A_dev, const int32_t* bands_dev,
+                   int n_mels, const float* twiddles_dev, const float* window_dev, float floor, float* mel_dev, void* stream);
+int df_wave_to_mel_tile(void);
+
 /* ---- packed-operand blob (multi-GPU weight distribution; replaces SURVEY's df_bcast_weights: the RCCL
  * communicator belongs to torch.distributed, so the library exports / imports and the host side broadcasts).
  * Root rank: load tensors, df_finalize, df_prepack (builds every operand packing the UNet CFG-batch 2B / VAE / cond plans
