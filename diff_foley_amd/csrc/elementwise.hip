@@ -677,17 +677,27 @@ inline int grid_for(long n, int block = 256, int cap = 4096) {
 
 }  // namespace
 
-size_t groupnorm_scratch_bytes(int N, int HW, int C) {
-  const long items = (long)HW * (C / 64);
-  if (items <= 16384 || (C != 128 && C != 256 && C != 512)) return 0;      // register kernels / generic streaming kernel
-  const int cpx = gn_stats_chunk_px(C), nchunk = (HW + cpx - 1) / cpx;
-  return ((size_t)N * nchunk * 32 * 2 + (size_t)N * 32 * 2) * sizeof(float);
+// The one GroupNorm rule (kernels.h).  Register kernel: thread layout R rows per pass x (cpg / 2) channel pairs, PER passes.
+GnRoute groupnorm_route(int N, int HW, int C, int nslab) {
+  if (C <= 0 || C % 64 != 0) return {GN_FORM_REFUSED, 0};
+  const int half = C / 64;
+  const long items = (long)HW * half;
+  const int rmax = std::min(HW, 1024 / half);
+  const int need = rmax > 0 ? (HW + rmax - 1) / rmax : 1 << 30;
+  if (items > 16384 || need > 20) {
+    if (nslab > 0) return {GN_FORM_REFUSED, 0};      // neither the streaming nor the chunked kernels have a slab path
+    if (items <= 16384 || (C != 128 && C != 256 && C != 512)) return {GN_FORM_STREAMING, 0};
+    const int cpx = gn_stats_chunk_px(C), nchunk = (HW + cpx - 1) / cpx;
+    return {GN_FORM_CHUNKED, ((size_t)N * nchunk * 32 * 2 + (size_t)N * 32 * 2) * sizeof(float)};
+  }
+  for (int per : {1, 2, 3, 4, 6, 8, 12, 16})
+    if (need <= per) return {per, 0};
+  return {20, 0};
 }
 
-hipError_t launch_groupnorm_chunked(const float* x, int ld, int N, int HW, int C, const float* gamma, const float* beta,
-                                    float eps, int silu, uint16_t* out, int ldo, uint16_t* raw_out, float* scratch,
-                                    hipStream_t s) {
-  if ((C != 128 && C != 256 && C != 512) || (ld & 3) || (ldo & 7) || !scratch) return hipErrorInvalidValue;
+static hipError_t groupnorm_chunked_launches(const GroupNormArgs& a, hipStream_t s) {
+  if ((a.ld & 3) || (a.ldo & 7) || !a.scratch) return hipErrorInvalidValue;
+  const int N = a.N, HW = a.HW, C = a.C;
   const int cpg = C / 32, cpx = gn_stats_chunk_px(C), nchunk = (HW + cpx - 1) / cpx;
   // apply chunk: 256 pixels, halved while the grid would not fill the chip twice (4 x 64 x 64 px at C = 512: 64 blocks of 256 px
   // ran the pass at 0.9 TB/s: 39 us per norm) and one chunk still feeds the eight pixels a thread keeps in flight
@@ -695,84 +705,42 @@ hipError_t launch_groupnorm_chunked(const float* x, int ld, int N, int HW, int C
   const int ppi = 256 / (C >> 3);
   while ((long)N * ((HW + chunk_apply - 1) / chunk_apply) < 512 && chunk_apply / 2 >= GN_APPLY_UN * ppi) chunk_apply /= 2;
   const int nchunk_apply = (HW + chunk_apply - 1) / chunk_apply;
-  float* part = scratch;
-  float* stat = scratch + (size_t)N * nchunk * 32 * 2;
-  hipLaunchKernelGGL(gn_chunk_stats_kernel, dim3(nchunk, N), dim3(256), 0, s, x, ld, HW, C, cpg, part);
-  hipLaunchKernelGGL(gn_merge_stats_kernel, dim3(32, N), dim3(64), 0, s, part, nchunk, cpx, HW, cpg, eps, stat);
-  hipLaunchKernelGGL(gn_chunk_apply_kernel, dim3(nchunk_apply, N), dim3(256), 0, s, x, ld, HW, C, cpg, gamma, beta, stat, silu,
-                     out, ldo, raw_out, chunk_apply);
+  float* part = a.scratch;
+  float* stat = a.scratch + (size_t)N * nchunk * 32 * 2;
+  hipLaunchKernelGGL(gn_chunk_stats_kernel, dim3(nchunk, N), dim3(256), 0, s, a.x, a.ld, HW, C, cpg, part);
+  hipLaunchKernelGGL(gn_merge_stats_kernel, dim3(32, N), dim3(64), 0, s, part, nchunk, cpx, HW, cpg, a.eps, stat);
+  hipLaunchKernelGGL(gn_chunk_apply_kernel, dim3(nchunk_apply, N), dim3(256), 0, s, a.x, a.ld, HW, C, cpg, a.gamma, a.beta, stat,
+                     a.silu, a.out, a.ldo, a.raw_out, chunk_apply);
   return hipGetLastError();
 }
 
-static hipError_t launch_groupnorm_sl(const float* x, int ld, int N, int HW, int C, const float* gamma, const float* beta,
-                                      float eps, int silu, uint16_t* out, int ldo, uint16_t* raw_out, const GnSlabs& sl,
-                                      hipStream_t s);
-
-hipError_t launch_groupnorm_slabs(const float* x, int ld, int N, int HW, int C, const float* gamma, const float* beta,
-                                  float eps, int silu, uint16_t* out, int ldo, uint16_t* raw_out, int nslab,
-                                  long slab_stride, const float* bias, const float* rowbias, int ld_rowbias, hipStream_t s) {
-  GnSlabs sl{nslab, slab_stride, bias, rowbias, ld_rowbias, nullptr, 0, nullptr, 0, nullptr};
-  return launch_groupnorm_sl(x, ld, N, HW, C, gamma, beta, eps, silu, out, ldo, raw_out, sl, s);
-}
-
-hipError_t launch_groupnorm_own_slabs(float* x, int ld, int N, int HW, int C, const float* gamma, const float* beta, float eps,
-                                      int silu, uint16_t* out, int ldo, uint16_t* raw_out, const float* slab0, int nslab,
-                                      long slab_stride, int c_own, const float* bias, const float* res, int ldr, hipStream_t s) {
-  if (nslab < 2 || !slab0 || c_own <= 0 || c_own > C || (c_own & 1) || (ld & 1) || (ldr & 1)) return hipErrorInvalidValue;
-  GnSlabs sl{nslab, slab_stride, bias, nullptr, 0, slab0, c_own, res, ldr, x};
-  return launch_groupnorm_sl(x, ld, N, HW, C, gamma, beta, eps, silu, out, ldo, raw_out, sl, s);
-}
-
-// The form launch_groupnorm_sl runs: PER of groupnorm_reg_kernel (thread layout: R rows per pass x (cpg / 2) channel pairs, PER
-// passes), GN_FORM_STREAMING, or GN_FORM_REFUSED (the streaming kernel has no slab path).
-static int groupnorm_sl_form(int HW, int C, int nslab) {
-  if (C <= 0 || C % 64 != 0) return GN_FORM_REFUSED;
-  const int half = C / 64;
-  const long items = (long)HW * half;
-  const int rmax = std::min(HW, 1024 / half);
-  const int need = rmax > 0 ? (HW + rmax - 1) / rmax : 1 << 30;
-  if (items > 16384 || need > 20) return nslab > 0 ? GN_FORM_REFUSED : GN_FORM_STREAMING;
-  for (int per : {1, 2, 3, 4, 6, 8, 12, 16})
-    if (need <= per) return per;
-  return 20;
-}
-
-bool groupnorm_accepts_slabs(int HW, int C) { return groupnorm_sl_form(HW, C, 1) != GN_FORM_REFUSED; }      // the register kernel's shapes
-
-int groupnorm_form(int N, int HW, int C, int nslab) {
-  if (nslab == 0 && groupnorm_scratch_bytes(N, HW, C)) return GN_FORM_CHUNKED;
-  return groupnorm_sl_form(HW, C, nslab);
-}
-
-static hipError_t launch_groupnorm_sl(const float* x, int ld, int N, int HW, int C, const float* gamma, const float* beta,
-                                      float eps, int silu, uint16_t* out, int ldo, uint16_t* raw_out, const GnSlabs& sl,
-                                      hipStream_t s) {
-  const int form = groupnorm_sl_form(HW, C, sl.n);
-  if (form == GN_FORM_REFUSED) return hipErrorInvalidValue;
-  const int cpg = C / 32, half = cpg / 2;
-#define DF_GN_REG(PER)                                                                                                \
-  case PER: {                                                                                                         \
-    const int R = (HW + (PER) - 1) / (PER);                                                                           \
-    const int threads = (half * R + 63) & ~63;                                                                        \
-    hipLaunchKernelGGL(groupnorm_reg_kernel<PER>, dim3(32 * N), dim3(threads), 0, s, x, ld, HW, cpg, R, sl.n, N, sl.own, \
-                       sl.c_own, sl.stride, out, ldo, silu, C, gamma, beta, eps, raw_out, sl);                        \
-    break;                                                                                                            \
+hipError_t launch_groupnorm(const GroupNormArgs& a, hipStream_t s) {
+  GnSlabs sl{a.nslab, a.slab_stride, a.bias, a.rowbias, a.ld_rowbias, nullptr, 0, nullptr, 0, nullptr};
+  if (a.own_slabs) {
+    if (a.nslab < 2 || a.c_own <= 0 || a.c_own > a.C || (a.c_own & 1) || (a.ld & 1) || (a.ldr & 1)) return hipErrorInvalidValue;
+    sl = GnSlabs{a.nslab, a.slab_stride, a.bias, nullptr, 0, a.own_slabs, a.c_own, a.res, a.ldr, const_cast<float*>(a.x)};
+  }
+  const int form = groupnorm_route(a.N, a.HW, a.C, a.nslab).form;
+  const int N = a.N, HW = a.HW, C = a.C, cpg = C / 32, half = cpg / 2;
+#define DF_GN_REG(PER)                                                                                                    \
+  case PER: {                                                                                                             \
+    const int R = (HW + (PER) - 1) / (PER);                                                                               \
+    const int threads = (half * R + 63) & ~63;                                                                            \
+    hipLaunchKernelGGL(groupnorm_reg_kernel<PER>, dim3(32 * N), dim3(threads), 0, s, a.x, a.ld, HW, cpg, R, sl.n, N, sl.own, \
+                       sl.c_own, sl.stride, a.out, a.ldo, a.silu, C, a.gamma, a.beta, a.eps, a.raw_out, sl);              \
+    break;                                                                                                                \
   }
   switch (form) {
+    case GN_FORM_CHUNKED: return groupnorm_chunked_launches(a, s);
     case GN_FORM_STREAMING:
-      hipLaunchKernelGGL(groupnorm_kernel, dim3(32, N), dim3(1024), 0, s, x, ld, HW, C, cpg, gamma, beta, eps, silu, out,
-                         ldo, raw_out);
+      hipLaunchKernelGGL(groupnorm_kernel, dim3(32, N), dim3(1024), 0, s, a.x, a.ld, HW, C, cpg, a.gamma, a.beta, a.eps, a.silu,
+                         a.out, a.ldo, a.raw_out);
       break;
     DF_GN_REG(1) DF_GN_REG(2) DF_GN_REG(3) DF_GN_REG(4) DF_GN_REG(6) DF_GN_REG(8) DF_GN_REG(12) DF_GN_REG(16) DF_GN_REG(20)
-    default: return hipErrorInvalidValue;
+    default: return hipErrorInvalidValue;      // GN_FORM_REFUSED
   }
 #undef DF_GN_REG
   return hipGetLastError();
-}
-
-hipError_t launch_groupnorm(const float* x, int ld, int N, int HW, int C, const float* gamma, const float* beta,
-                            float eps, int silu, uint16_t* out, int ldo, uint16_t* raw_out, hipStream_t s) {
-  return launch_groupnorm_slabs(x, ld, N, HW, C, gamma, beta, eps, silu, out, ldo, raw_out, 0, 0, nullptr, nullptr, 0, s);
 }
 
 hipError_t launch_layernorm(const float* x, int ld, int rows, int C, const float* gamma, const float* beta,

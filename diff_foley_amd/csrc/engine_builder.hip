@@ -163,52 +163,57 @@ void Builder::add_a2(GemmParams& g, const bf16_t* A2, int lda2, int Cin2) {
   g.w_bytes = op_bytes((size_t)g.N * g.K * 2);
 }
 
+// The one place a plan emits a GroupNorm: asks the route (csrc/kernels.h), allocates the scratch that route wants, pushes the op,
+// records its outputs and releases the scratch.  feed != GnFeed::none: the GEMM at ops[prod] may be tuned to split-K AFTER the build,
+// so where the register kernels hold this shape its reduce is left to the norm (Op::defer) and every launch looks at the producer
+// again: split-K -> the slab fields of its own copy of the descriptor are filled in, otherwise the plain norm runs.
+void Builder::emit_groupnorm(GroupNormArgs a, GnFeed feed, size_t prod, const float* rowbias, int ld_rowbias) {
+  const size_t sb = groupnorm_route(a.N, a.HW, a.C, 0).scratch_bytes;
+  if (feed != GnFeed::none && groupnorm_route(a.N, a.HW, a.C, 1).form == GN_FORM_REFUSED) feed = GnFeed::none;
+  if (feed != GnFeed::none) pl->ops[prod].defer = true;
+  a.scratch = sb ? (float*)pl->alloc(sb) : nullptr;
+  Plan* plp = pl;
+  other("groupnorm", [=](hipStream_t s, const RunArgs&) {
+    if (feed == GnFeed::none) return launch_groupnorm(a, s);
+    const GemmParams& gp = plp->ops[prod].gp;
+    if (!plp->ops[prod].defer || gp.splitk <= 1) return launch_groupnorm(a, s);
+    GroupNormArgs g = a;
+    g.nslab = gp.splitk;
+    g.slab_stride = (long)gp.M * gp.N;
+    g.bias = gp.bias;
+    if (feed == GnFeed::input_slabs) {      // the producer's output has this norm as its ONE reader: it is never written
+      g.x = gp.partial;
+      g.rowbias = rowbias;
+      g.ld_rowbias = ld_rowbias;
+    } else {                                // own slabs: this norm finishes x (bias + residual, in the reduce kernel's order) and writes it back
+      g.own_slabs = gp.partial;
+      g.c_own = gp.N;
+      g.res = gp.res;
+      g.ldr = gp.ldr;
+    }
+    return launch_groupnorm(g, s);
+  });
+  emits(a.out, (long)a.N * a.HW, a.C, a.ldo);
+  emits(a.raw_out, (long)a.N * a.HW, a.C, a.ldo);
+  pl->release(a.scratch);
+}
+
 bf16_t* Builder::groupnorm(const F32& x, int NB, const std::string& p, float eps, int silu, bf16_t** raw) {
   bf16_t* o = buf<bf16_t>((size_t)x.rows * x.C);
   bf16_t* r = raw ? buf<bf16_t>((size_t)x.rows * x.C) : nullptr;
   if (raw) *raw = r;
-  const float* g = c->f32(nm(p + ".weight"));
-  const float* b = c->f32(nm(p + ".bias"));
-  const float* xp = x.p;
-  const int ld = x.ld, HW = x.rows / NB, C = x.C;
-  const size_t sb = groupnorm_scratch_bytes(NB, HW, C);
+  GroupNormArgs a;
+  a.x = x.p; a.ld = x.ld; a.N = NB; a.HW = x.rows / NB; a.C = x.C;
+  a.gamma = c->f32(nm(p + ".weight")); a.beta = c->f32(nm(p + ".bias")); a.eps = eps; a.silu = silu;
+  a.out = o; a.ldo = x.C; a.raw_out = r;
   // x straight out of a GEMM that may run split-K (a ResBlock's conv2, a SpatialTransformer's merged FF2 + proj_out, a
   // Downsample conv): this norm is its first reader, so it does the reduce -- sums the slabs, adds bias + residual, writes
   // x back -- in the launch it needs anyway; the producer's reduce launch and one fp32 round trip of x disappear.
   static const bool no_own = getenv("DF_NO_GNOWN") && atoi(getenv("DF_NO_GNOWN"));
-  Pend pd = pend;
-  if (!no_own && !sb && pd.op >= 0 && pd.p == xp && pd.ld == ld && pd.rows == x.rows && pd.C <= C && (pd.C & 1) == 0 &&
-      (ld & 1) == 0 && groupnorm_accepts_slabs(HW, C)) {
-    Plan* plp = pl;
-    const size_t pi = (size_t)pd.op;
-    pl->ops[pi].defer = true;
-    float* xw = x.p;
-    other("groupnorm", [=](hipStream_t s, const RunArgs&) {
-      const Op& po = plp->ops[pi];
-      if (po.defer && po.gp.splitk > 1)
-        return launch_groupnorm_own_slabs(xw, ld, NB, HW, C, g, b, eps, silu, o, C, r, po.gp.partial, po.gp.splitk,
-                                          (long)po.gp.M * po.gp.N, po.gp.N, po.gp.bias, po.gp.res, po.gp.ldr, s);
-      return launch_groupnorm(xp, ld, NB, HW, C, g, b, eps, silu, o, C, r, s);
-    });
-    emits(o, x.rows, C, C);
-    emits(r, x.rows, C, C);
-    return o;
-  }
-  if (sb) {          // large slabs (VAE decoder): pixel-chunked, fully coalesced three-launch form
-    float* scr = (float*)pl->alloc(sb);
-    other("groupnorm", [=](hipStream_t s, const RunArgs&) {
-      return launch_groupnorm_chunked(xp, ld, NB, HW, C, g, b, eps, silu, o, C, r, scr, s);
-    });
-    emits(o, x.rows, C, C);
-    emits(r, x.rows, C, C);
-    pl->release(scr);
-    return o;
-  }
-  other("groupnorm", [=](hipStream_t s, const RunArgs&) {
-    return launch_groupnorm(xp, ld, NB, HW, C, g, b, eps, silu, o, C, r, s);
-  });
-  emits(o, x.rows, C, C);
-  emits(r, x.rows, C, C);
+  const Pend pd = pend;
+  const bool claim = !no_own && pd.op >= 0 && pd.p == x.p && pd.ld == x.ld && pd.rows == x.rows && pd.C <= x.C && (pd.C & 1) == 0 &&
+                     (x.ld & 1) == 0;
+  emit_groupnorm(a, claim ? GnFeed::own_slabs : GnFeed::none, claim ? (size_t)pd.op : 0, nullptr, 0);
   return o;
 }
 
@@ -254,27 +259,13 @@ void Builder::resblock(const F32& x, const F32& out, int NB, int H, int Wd, cons
   // h1 has ONE consumer, the second GroupNorm.  When conv1 runs split-K, its reduce launch is dropped: the norm sums
   // the partial slabs while loading and adds the bias / FiLM bias itself (no reduce kernel, no fp32 round trip of h1).
   const size_t ci = pl->ops.size() - 1;
-  pl->ops[ci].defer = groupnorm_accepts_slabs(H * Wd, cout);
   bf16_t* a2 = buf<bf16_t>((size_t)M * cout);
   {
-    Plan* plp = pl;
-    const float* gm = c->f32(nm(n2 + ".weight"));
-    const float* bt = c->f32(nm(n2 + ".bias"));
-    const float* cb = c->f32(nm(c1 + ".bias"));
-    const float* rb = emb ? emb + emb_col : nullptr;
-    const int HW = H * Wd;
-    const size_t sb = groupnorm_scratch_bytes(NB, HW, cout);
-    float* scr = sb ? (float*)pl->alloc(sb) : nullptr;
-    other("groupnorm", [=](hipStream_t s, const RunArgs&) {
-      const Op& co = plp->ops[ci];
-      if (co.defer && co.gp.splitk > 1)
-        return launch_groupnorm_slabs(co.gp.partial, cout, NB, HW, cout, gm, bt, eps, 1, a2, cout, nullptr, co.gp.splitk,
-                                      (long)M * cout, cb, rb, emb_ld, s);
-      if (scr) return launch_groupnorm_chunked(h1, cout, NB, HW, cout, gm, bt, eps, 1, a2, cout, nullptr, scr, s);
-      return launch_groupnorm(h1, cout, NB, HW, cout, gm, bt, eps, 1, a2, cout, nullptr, s);
-    });
-    emits(a2, M, cout, cout);
-    pl->release(scr);
+    GroupNormArgs a;
+    a.x = h1; a.ld = cout; a.N = NB; a.HW = H * Wd; a.C = cout;
+    a.gamma = c->f32(nm(n2 + ".weight")); a.beta = c->f32(nm(n2 + ".bias")); a.eps = eps; a.silu = 1;
+    a.out = a2; a.ldo = cout;
+    emit_groupnorm(a, GnFeed::input_slabs, ci, emb ? emb + emb_col : nullptr, emb_ld);
   }
   pl->release(h1);
   {

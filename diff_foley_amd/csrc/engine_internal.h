@@ -435,6 +435,11 @@ struct Builder {
   static void out_f32(GemmParams& g, float* C, int ldc) { g.C = C; g.ldc = ldc; g.out_bf16 = 0; }
   static void out_b16(GemmParams& g, bf16_t* C, int ldc) { g.C = C; g.ldc = ldc; g.out_bf16 = 1; }
 
+  // Both norms of a plan go through emit_groupnorm (engine_builder.hip).  A split-K producer at ops[prod] hands its reduce to the norm
+  // in one of two ways: input_slabs -- the norm sums the slabs of its INPUT (a ResBlock's conv1 -> second norm; + bias + FiLM row
+  // bias); own_slabs -- the norm finishes the slabs of the tensor it normalises and writes it back (the claimed `pend` GEMM).
+  enum class GnFeed { none, input_slabs, own_slabs };
+  void emit_groupnorm(GroupNormArgs a, GnFeed feed, size_t prod, const float* rowbias, int ld_rowbias);
   // GroupNorm(+SiLU) -> bf16 operand (and optionally the raw bf16 cast)
   bf16_t* groupnorm(const F32& x, int NB, const std::string& p, float eps, int silu, bf16_t** raw);
   void layernorm(const F32& x, const std::string& p, bf16_t* o);

@@ -593,32 +593,26 @@ int df_test_conv3x3_down_valid(int NB, int H, int Wd, int Cin, int Cout, int pad
   }
 }
 
-// Which kernel form a shape takes (host only; csrc/kernels.h groupnorm_form / attention_form -- the functions the launchers
+// Which kernel form a shape takes (host only; csrc/kernels.h groupnorm_route / attention_form -- the functions the launchers
 // themselves dispatch on): tests/test_kernel_forms_cpu.py asserts that the GPU tests' shape tables reach every form.
 int df_test_groupnorm_form(int N, int HW, int C, int nslab) { return groupnorm_form(N, HW, C, nslab); }
 int df_test_attention_form(int D, int Tq, int Tk) { return attention_form(D, Tq, Tk); }
 
-// GroupNorm in its three input modes with every leading dimension free: plain (nslab == 0; the chunked form where
-// groupnorm_form says so), a split-K producer's slabs (nslab > 0: x is the first slab, + bias + rowbias) and the norm's own
-// producer (own_slabs != null: df_test_groupnorm_own_slabs with ldo / raw_out).  raw_out rows are ldo wide like out's.
+// GroupNorm in its three input modes with every leading dimension free: plain (nslab == 0), a split-K producer's slabs
+// (nslab > 0: x is the first slab, + bias + rowbias) and the norm's own producer (own_slabs != null: df_test_groupnorm_own_slabs
+// with ldo / raw_out).  raw_out rows are ldo wide like out's.  The arguments become the launcher's descriptor as they are.
 int df_test_groupnorm_ex(float* x, int ld, int N, int HW, int C, const float* gamma, const float* beta, float eps, int silu,
                          uint16_t* out, int ldo, uint16_t* raw_out, int nslab, int64_t slab_stride, const float* bias,
                          const float* rowbias, int ld_rowbias, const float* own_slabs, int c_own, const float* res, int ldr,
                          void* stream) {
   return guard([&] {
-    hipStream_t s = (hipStream_t)stream;
-    const int form = groupnorm_form(N, HW, C, nslab);
-    if (form == GN_FORM_REFUSED) fail("groupnorm: %d x %d with %d slabs is refused", HW, C, nslab);
-    if (own_slabs) {
-      HIPCHK(launch_groupnorm_own_slabs(x, ld, N, HW, C, gamma, beta, eps, silu, out, ldo, raw_out, own_slabs, nslab, (long)slab_stride,
-                                        c_own, bias, res, ldr, s));
-    } else if (form == GN_FORM_CHUNKED) {
-      float* scr = test_partial(groupnorm_scratch_bytes(N, HW, C));
-      HIPCHK(launch_groupnorm_chunked(x, ld, N, HW, C, gamma, beta, eps, silu, out, ldo, raw_out, scr, s));
-    } else {
-      HIPCHK(launch_groupnorm_slabs(x, ld, N, HW, C, gamma, beta, eps, silu, out, ldo, raw_out, nslab, (long)slab_stride, bias, rowbias,
-                                    ld_rowbias, s));
-    }
+    GroupNormArgs a;
+    a.x = x; a.ld = ld; a.N = N; a.HW = HW; a.C = C; a.gamma = gamma; a.beta = beta; a.eps = eps; a.silu = silu;
+    a.out = out; a.ldo = ldo; a.raw_out = raw_out;
+    a.nslab = nslab; a.slab_stride = (long)slab_stride; a.bias = bias; a.rowbias = rowbias; a.ld_rowbias = ld_rowbias;
+    a.own_slabs = own_slabs; a.c_own = c_own; a.res = res; a.ldr = ldr;
+    a.scratch = test_partial(groupnorm_route(N, HW, C, nslab).scratch_bytes);
+    HIPCHK(launch_groupnorm(a, (hipStream_t)stream));
   });
 }
 int df_test_groupnorm(const float* x, int ld, int N, int HW, int C, const float* gamma, const float* beta, float eps,

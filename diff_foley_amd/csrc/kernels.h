@@ -3,35 +3,53 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-// GroupNorm(32 groups) [+ SiLU] over an fp32 NHWC tensor [N][HW][ld] -> bf16 [N][HW][ldo].
-// raw_out (optional) receives the un-normalised input cast to bf16 (operand of a 1x1 skip conv).
-hipError_t launch_groupnorm(const float* x, int ld, int N, int HW, int C, const float* gamma, const float* beta,
-                            float eps, int silu, uint16_t* out, int ldo, uint16_t* raw_out, hipStream_t s);
-
-// Same with a split-K producer: x = first fp32 partial slab [rows][ld] of the conv that feeds this norm; the kernel sums
-// nslab slabs (slab_stride floats apart) and adds the conv's bias / per-sample bias on the fly (nslab = 0: plain input).
-hipError_t launch_groupnorm_slabs(const float* x, int ld, int N, int HW, int C, const float* gamma, const float* beta,
-                                  float eps, int silu, uint16_t* out, int ldo, uint16_t* raw_out, int nslab,
-                                  long slab_stride, const float* bias, const float* rowbias, int ld_rowbias, hipStream_t s);
-bool groupnorm_accepts_slabs(int HW, int C);
-// The form a GroupNorm of this shape runs: PER of the register kernel (1, 2, 3, 4, 6, 8, 12, 16 or 20), or one of the codes below.
-// nslab > 0: a split-K producer's slabs are summed on the fly (either slab path); nslab == 0 includes the callers' switch to
-// launch_groupnorm_chunked when groupnorm_scratch_bytes() is non-zero.  launch_groupnorm* dispatch on this function.
+// GroupNorm(32 groups) [+ SiLU] over an fp32 NHWC tensor [N][HW][ld] -> operand type [N][HW][ldo].  ONE rule decides the kernel:
+// groupnorm_route(N, HW, C, nslab) -- the form and the scratch that form needs -- and launch_groupnorm obeys it; plans
+// (Builder::emit_groupnorm) and tests (df_test_groupnorm_form, df_test_groupnorm_ex) ask that same function.
+//   form  PER of the register kernel (1, 2, 3, 4, 6, 8, 12, 16 or 20: at most 16384 float2 per group, read from memory once);
+//         GN_FORM_STREAMING   larger groups, generic three-pass kernel;
+//         GN_FORM_CHUNKED     larger groups with C in {128, 256, 512} (VAE): pixel-chunked three-launch form with fully coalesced
+//                             rows, which needs scratch_bytes of `scratch`, ld % 4 == 0 and ldo % 8 == 0;
+//         GN_FORM_REFUSED     C is no multiple of 64, or slabs (nslab > 0) on a shape the register kernels do not hold.
+// launch_groupnorm returns hipErrorInvalidValue, and launches nothing, for a refused route, a chunked route without scratch or
+// with misaligned rows, and own slabs that break the rules below.
 enum { GN_FORM_STREAMING = -1, GN_FORM_CHUNKED = -2, GN_FORM_REFUSED = -3 };
-int groupnorm_form(int N, int HW, int C, int nslab);
-// x is the NOT-YET-REDUCED output of its own split-K producer: channels [0, c_own) are summed from nslab slabs (leading
-// dimension c_own), bias and the fp32 residual `res` are added in the reduce kernel's order and the result is written back
-// to x before it is normalised; channels [c_own, C) are read from x (the skip half of a concat buffer).
-hipError_t launch_groupnorm_own_slabs(float* x, int ld, int N, int HW, int C, const float* gamma, const float* beta, float eps,
-                                      int silu, uint16_t* out, int ldo, uint16_t* raw_out, const float* slab0, int nslab,
-                                      long slab_stride, int c_own, const float* bias, const float* res, int ldr, hipStream_t s);
+struct GnRoute {
+  int form;
+  size_t scratch_bytes;
+};
+GnRoute groupnorm_route(int N, int HW, int C, int nslab);
+inline int groupnorm_form(int N, int HW, int C, int nslab) { return groupnorm_route(N, HW, C, nslab).form; }
 
-// Large slabs (VAE decoder, C in {128, 256, 512}, more than 16384 float2 per group): pixel-chunked three-launch form with
-// fully coalesced rows; `scratch` holds groupnorm_scratch_bytes(N, HW, C) bytes (0 = shape not handled: use launch_groupnorm).
-size_t groupnorm_scratch_bytes(int N, int HW, int C);
-hipError_t launch_groupnorm_chunked(const float* x, int ld, int N, int HW, int C, const float* gamma, const float* beta,
-                                    float eps, int silu, uint16_t* out, int ldo, uint16_t* raw_out, float* scratch,
-                                    hipStream_t s);
+struct GroupNormArgs {
+  // the tensor and the norm; raw_out (optional) receives the un-normalised input cast to the operand type (a 1x1 skip conv's operand)
+  const float* x = nullptr;
+  int ld = 0, N = 0, HW = 0, C = 0;
+  const float* gamma = nullptr;
+  const float* beta = nullptr;
+  float eps = 0.f;
+  int silu = 0;
+  uint16_t* out = nullptr;
+  int ldo = 0;
+  uint16_t* raw_out = nullptr;
+  // input slabs (nslab > 0, own_slabs null): x = first fp32 partial slab [rows][ld] of the split-K conv that feeds this norm; the kernel
+  // sums nslab slabs (slab_stride floats apart) and adds the conv's bias / per-sample bias on the fly
+  int nslab = 0;
+  long slab_stride = 0;
+  const float* bias = nullptr;
+  const float* rowbias = nullptr;
+  int ld_rowbias = 0;
+  // own slabs (own_slabs != null): x is the NOT-YET-REDUCED output of its own split-K producer: channels [0, c_own) are summed from
+  // nslab >= 2 slabs (leading dimension c_own), bias and the fp32 residual `res` are added in the reduce kernel's order and the
+  // result is WRITTEN BACK to x before it is normalised; channels [c_own, C) are read from x (the skip half of a concat buffer).
+  // 0 < c_own <= C; c_own, ld and ldr even.
+  const float* own_slabs = nullptr;
+  int c_own = 0;
+  const float* res = nullptr;
+  int ldr = 0;
+  float* scratch = nullptr;      // GnRoute::scratch_bytes of the plain (nslab == 0) route, or null where that is 0
+};
+hipError_t launch_groupnorm(const GroupNormArgs& a, hipStream_t s);
 
 // LayerNorm over the last dim of fp32 [rows][ld] -> bf16 [rows][C]   (eps 1e-5, affine)
 hipError_t launch_layernorm(const float* x, int ld, int rows, int C, const float* gamma, const float* beta,

@@ -202,6 +202,59 @@ def test_groupnorm_every_form(case):
     check_elementwise(got, y64, y32, f"groupnorm {mode} form {form}")
 
 
+def test_groupnorm_refusals_launch_nothing():
+    """The smallest shape on the wrong side of each rule of the GroupNorm launcher: every such call returns non-zero with
+    df_last_error() set and leaves out, raw_out and x bit-identical.  The one shape right next to a refusal that must run
+    (input slabs at HW = 16384, C = 64: PER 16, the most the register kernels hold) is checked with the file's bound."""
+    L = _eng().lib(PREC)
+    keep = []
+    dev = lambda t: (keep.append(t.cuda()), keep[-1])[1]
+
+    def call(x, ld, N, HW, Cc, ldo, nslab=0, stride=0, bias=None, own=None, c_own=0, res=None, ldr=0):
+        g, b = dev(rnd((Cc,), 7) * 0.5 + 1.0), dev(rnd((Cc,), 8))
+        out, raw = sentinel((N * HW + 1, ldo)), sentinel((N * HW + 1, ldo))
+        rc = L.df_test_groupnorm_ex(ptr(x), ld, N, HW, Cc, ptr(g), ptr(b), 1e-5, 1, ptr(out), ldo, ptr(raw), nslab, stride, ptr(bias),
+                                    None, 0, ptr(own), c_own, ptr(res), ldr, stream())
+        torch.cuda.synchronize()
+        return rc, out.cpu(), raw.cpu()
+
+    def refused(what, x, *a, **kw):
+        before = x.clone()
+        rc, out, raw = call(x, *a, **kw)
+        assert rc != 0 and L.df_last_error(), f"{what}: not refused"
+        assert is_sentinel(out) and is_sentinel(raw), f"{what}: a refused call wrote its outputs"
+        assert torch.equal(x.view(torch.int32), before.view(torch.int32)), f"{what}: a refused call wrote x"
+
+    # input slabs: one item more than the register kernels hold, then the largest shape they do hold
+    slabs = rnd((2, 16385, 64), 61) * 0.9 + 0.2
+    bias = rnd((64,), 62)
+    xs, bs = dev(slabs), dev(bias)
+    refused("slabs HW 16385", xs, 64, 1, 16385, 64, 64, nslab=2, stride=16385 * 64, bias=bs)
+    assert L.df_test_groupnorm_form(1, 16384, 64, 2) == 16
+    rc, out, raw = call(xs, 64, 1, 16384, 64, 64, nslab=2, stride=16385 * 64, bias=bs)
+    assert rc == 0, L.df_last_error()
+    assert torch.equal(xs.cpu(), slabs), "a producer's slabs are read-only"
+    full = (slabs[0, :16384] + slabs[1, :16384]) + bias
+    assert is_sentinel(out[16384]) and is_sentinel(raw[16384])
+    assert torch.equal(bits(raw[:16384]), bits(full.to(odt()))), "raw_out is not the input rounded to nearest"
+    nchw = lambda t: t.reshape(1, 16384, 64).permute(0, 2, 1)
+    g, b = rnd((64,), 7) * 0.5 + 1.0, rnd((64,), 8)
+    y64 = F.silu(F.group_norm(nchw(full.double()), 32, g.double(), b.double(), 1e-5))
+    y32 = F.silu(F.group_norm(nchw(full), 32, g, b, 1e-5))
+    check_elementwise(nchw(out[:16384]), y64, y32, "groupnorm slabs form 16 (HW 16384)")
+
+    # own slabs: an odd c_own, a single slab, an odd residual leading dimension
+    for what, c_own, nslab, ldr in (("c_own 31", 31, 2, 32), ("nslab 1", 32, 1, 32), ("ldr 33", 32, 2, 33)):
+        own, ob, res = dev(rnd((nslab, 16, c_own), 61)), dev(rnd((c_own,), 62)), dev(rnd((16, ldr), 63))
+        refused("own slabs " + what, dev(rnd((16, 64), 64)), 64, 1, 16, 64, 64, nslab=nslab, stride=16 * c_own, bias=ob, own=own,
+                c_own=c_own, res=res, ldr=ldr)
+
+    # plain: a chunked shape whose output rows are not 16-byte aligned; a channel count that is no multiple of 64
+    assert L.df_test_groupnorm_form(1, 8193, 128, 0) == KC.GN_CHUNKED
+    refused("chunked ldo C + 4", dev(rnd((8193, 128), 6)), 128, 1, 8193, 128, 132)
+    refused("C 100", dev(rnd((16, 100), 6)), 100, 1, 16, 100, 100)
+
+
 # ------------------------------------------------------------------------------------------------------------------- LayerNorm
 @pytest.mark.parametrize("rows,Cc,ld", KC.LN_CASES)
 def test_layernorm_every_width(rows, Cc, ld):
