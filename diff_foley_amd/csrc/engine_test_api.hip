@@ -111,6 +111,37 @@ int df_test_gemm_key(const df_test_gemm_desc* d, int batch, char* buf, int n) {
   }
 }
 
+int df_test_gemm_launch_constants(const df_test_gemm_desc* d, int tile, int batch, int splitk, df_test_gemm_launch* out) {
+  std::lock_guard<std::recursive_mutex> hold(g_api_lock);
+  try {
+    if (!out || out->size != (int64_t)sizeof(df_test_gemm_launch)) fail("df_test_gemm_launch_constants: a df_test_gemm_launch of another size");
+    GemmParams g;
+    test_gemm_params(d, g);
+    GemmRoute r;
+    if (const char* why = gemm_route(g, tile, batch, splitk, &r)) {
+      g_err = std::string("df_test_gemm_launch_constants: launch_gemm refuses this problem (") + why + ")";
+      return 2;
+    }
+    GemmLaunch c;
+    gemm_launch_consts(g, tile, splitk, r, &c);
+    out->nbm = c.nbm; out->nbn = c.nbn; out->nblk = c.nblk; out->xq = c.xq; out->xr = c.xr; out->gm = c.gm;
+    const GemmMagic* mg[7] = {&c.per, &c.rows, &c.last, &c.wrb, &c.ohw, &c.ow, &c.cin};
+    for (int i = 0; i < 7; ++i) {
+      out->magic[i].mul = mg[i]->mul; out->magic[i].sh = mg[i]->sh; out->magic[i].d = mg[i]->d;
+    }
+    out->nk = c.nk; out->kper = c.kper; out->n2tot = c.n2tot; out->used = c.used; out->per2 = c.per2;
+    out->HWp = c.HWp; out->PPX = c.PPX; out->PB = c.PB; out->HR = c.HR; out->APASS = c.APASS;
+    out->npx = c.npx; out->npy = c.npy; out->pimg = c.pimg; out->npatch = c.npatch;
+    out->inv_hwp = c.inv_hwp; out->inv_tw2 = c.inv_tw2; out->inv_pimg = c.inv_pimg; out->inv_npx = c.inv_npx;
+    out->inv_ppx = c.inv_ppx; out->inv_tw = c.inv_tw;
+    out->th = r.th; out->tw = r.tw;
+    return 0;
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return -1;
+  }
+}
+
 int df_test_gemm_tile_info(int tile, df_test_gemm_tile* out) {
   std::lock_guard<std::recursive_mutex> hold(g_api_lock);
   if (tile < 0 || tile >= TILE_ALL || !out || out->size != (int64_t)sizeof(df_test_gemm_tile)) {

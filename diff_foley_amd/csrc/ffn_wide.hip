@@ -57,16 +57,11 @@ __global__ __launch_bounds__(512, 2) void geglu_wide_kernel(GemmParams p) {
   stamp();
 
   // ---- tile id: each XCD owns a contiguous range of logical tiles (block b runs on XCD b % 8), walked by p.gm like the generic kernel
-  const int nbm = (p.M + BM - 1) / BM, nbn = p.N / BN, nblk = nbm * nbn;
-  int lid;
-  {
-    const int bid = blockIdx.x, q = nblk >> 3, r = nblk & 7, xcd = bid & 7, idx = bid >> 3;
-    lid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  // (tile counts, the walk and the K steps come from the host: GemmLaunch, gemm.h -- nothing is divided here)
   int mt, nt;
-  tile_of(lid, nbm, nbn, p.gm, mt, nt);
+  tile_of_lc(p.lc, blockIdx.x, mt, nt);
   const int m0 = mt * BM, n0 = nt * BN;
-  const int nk = p.K / BK;
+  const int nk = p.lc.nk;
 
   const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, (int)p.a_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc((void*)p.W_w320, 0, (int)p.w_bytes, 0x00020000);
@@ -76,10 +71,10 @@ __global__ __launch_bounds__(512, 2) void geglu_wide_kernel(GemmParams p) {
 #pragma unroll
   for (int i = 0; i < AP; ++i) {
     const int m = m0 + r0 + RPP * i;
-    a_off[i] = m < p.M ? (unsigned)(((long)m * p.lda + c8) * 2) : OOB;
+    a_off[i] = m < p.M ? ((unsigned)m * (unsigned)p.lda + (unsigned)c8) * 2u : OOB;
   }
 #pragma unroll
-  for (int i = 0; i < BP; ++i) b_off[i] = (unsigned)(((long)(n0 + r0 + RPP * i) * p.K + c8) * 2);
+  for (int i = 0; i < BP; ++i) b_off[i] = ((unsigned)(n0 + r0 + RPP * i) * (unsigned)p.K + (unsigned)c8) * 2u;
   char* const dma0 = smem + wid * (8 * BK * 2);
   // one stage: every wavefront writes 8 rows x 128 B (1 KiB, lane-linear) per instruction.  Stages past the end of K are requested
   // out of bounds (the hardware writes zeros into a slot nobody reads), so the request count per step is constant and the waits
@@ -304,8 +299,7 @@ hipError_t launch_wgeglu(const GemmParams& p, hipStream_t stream) {
     if (e != hipSuccess) return e;
     attr_set = true;
   }
-  const int nblk = ((p.M + BM - 1) / BM) * (p.N / 320);
-  hipLaunchKernelGGL((geglu_wide_kernel<RT, NST, DBG>), dim3(nblk), dim3(512), lds, stream, p);
+  hipLaunchKernelGGL((geglu_wide_kernel<RT, NST, DBG>), dim3(p.lc.nblk), dim3(512), lds, stream, p);
   return hipGetLastError();
 }
 

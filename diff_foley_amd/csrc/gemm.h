@@ -12,12 +12,39 @@
 #include <stdint.h>
 #include "common.h"
 
+// Launch constants (gemm_launch_consts, gemm.hip): everything a block's prologue would otherwise derive from GemmParams by dividing by
+// constants of the launch -- tile counts, the tile walk, the K range of a split, the halo geometry -- and, for every divisor the
+// device still applies, what turns the division into a multiplication.  Computed on the host once per launch, read-only on the
+// device: a prologue holds no division, integer or float (tools/check_prologue.py).  Two forms:
+//   GemmMagic   x / d == umulhi(x, mul) >> sh for 0 <= x < 2^31 (d == 1: x).  Block-uniform quotients -- the tile walk, the weight
+//               matrix of a tile, the first tap of a split -- stay on the scalar unit with it (a float reciprocal would take them,
+//               and every address computed from them, through vector registers), and conv rows may pass 2^22.
+//   reciprocals the IEEE 1.0f / (float)d of FastDiv (gemm_impl.h), exact for 0 <= x < 2^22: the halo kernels' per-thread quotients.
+struct GemmMagic { unsigned mul; int sh; int d; };
+struct GemmLaunch {
+  // tile walk: blockIdx.x -> logical tile id (XCD remap: xq = nblk / 8, xr = nblk % 8) -> (M tile, N tile)
+  int nbm, nbn, nblk, xq, xr;
+  int gm;                      // M tiles per row group, normalised to 1 .. nbm (GemmParams::gm <= 0 or >= nbm: one group)
+  GemmMagic per, rows, last;   // by gm * nbn (logical tiles of a full row group), by gm, by the M tiles of the last (short) row group
+  // K range of a split: split z runs K steps (halo tiles: 64-channel slices) [z * kper, min(nk, (z + 1) * kper))
+  int nk, kper;
+  // halo tiles' folded skip: its n2tot slices are dealt, per2 each, to the `used` splits that own conv slices (no split-K: used = 1)
+  int n2tot, used, per2;
+  GemmMagic wrb;               // per-sample weights: by the M tiles per weight matrix (w_rows / BM); d = 0: off
+  GemmMagic ohw, ow, cin;      // MODE 1 .. 3: row -> (sample, y, x) by OH OW and OW, first K index of a split -> tap by Cin
+  // halo tiles: (TH + 2)(TW + 2), TH TW, patches per block, halo rows, DMA passes of a halo, patches per image row / column / image
+  // and in all
+  int HWp, PPX, PB, HR, APASS, npx, npy, pimg, npatch;
+  float inv_hwp, inv_tw2, inv_pimg, inv_npx, inv_ppx, inv_tw;
+};
+
 struct GemmParams {
   // operands
   const uint16_t* A; long a_bs; int lda;
   const uint16_t* W; long w_bs;
   unsigned a_bytes, w_bytes;   // bytes addressable from A / W of ONE batch slice (buffer-load bounds, < 2 GiB)
   int M, N, K;
+  GemmLaunch lc;               // set by launch_gemm from the route; beside the operands, which the first requests need with it
   // implicit-conv geometry
   // ResBlock skip connection folded into conv2 (openai_unetmodel.py:234-241, 275: skip(x) + h): a TENTH K range of
   // Cin2 channels read from a second operand tensor at the centre pixel, K = 9*Cin + Cin2, W rows = [conv taps | skip]
@@ -163,6 +190,10 @@ struct GemmRoute {
   int th, tw, halo_ring_bytes;                 // halo tiles: the block's patch of output pixels, bytes of its LDS operand ring
   size_t lds;                                  // halo tiles: dynamic LDS of the launch
 };
+// The launch constants of a problem the route admits (r = what gemm_route said for the same p, tile, splitk): the ONE place that
+// derives them; the kernels are their only reader.  Pure host arithmetic.
+void gemm_launch_consts(const GemmParams& p, int tile, int splitk, const GemmRoute& r, GemmLaunch* out);
+GemmMagic gemm_magic(int d);
 // nullptr: the tile can run this problem at this batch and split-K, *out (may be null) says how; else the rule that refuses.
 // Every correctness rule of the GEMM stack is here, once; pure host arithmetic, no HIP call.
 const char* gemm_route(const GemmParams& p, int tile, int batch, int splitk, GemmRoute* out);

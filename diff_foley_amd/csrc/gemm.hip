@@ -326,6 +326,63 @@ const char* gemm_route(const GemmParams& p, int tile, int batch, int splitk, Gem
   return nullptr;
 }
 
+GemmMagic gemm_magic(int d) {
+  // l = ceil(log2 d); mul = floor(2^(31 + l) / d) + 1 < 2^32 (d > 2^(l - 1)); mul d = 2^(31 + l) + e with 0 < e <= d <= 2^l, so
+  // x mul / 2^(31 + l) = x / d + x e / (d 2^(31 + l)) and the excess stays below 1 / d for x < 2^31: the floor is x / d.
+  // (d == 1 has no 32-bit multiplier: the device returns x.)
+  GemmMagic m{0u, 0, d};
+  if (d < 2) return m;
+  int l = 1;
+  while (l < 31 && (1l << l) < (long)d) ++l;
+  m.mul = (unsigned)((((unsigned long)1 << (31 + l)) / (unsigned long)d) + 1);
+  m.sh = l - 1;
+  return m;
+}
+
+void gemm_launch_consts(const GemmParams& p, int tile, int splitk, const GemmRoute& r, GemmLaunch* out) {
+  GemmLaunch c{};
+  const GemmTileInfo& t = kGemmTiles[tile];
+  const auto inv = [](int d) { return 1.0f / (float)std::max(d, 1); };     // FastDiv's reciprocal (gemm_impl.h)
+  const int sk = splitk > 1 ? splitk : 1;
+  const bool halo = r.family == DF_FAM_HALO;
+  if (halo) {
+    const int TH = r.th, TW = r.tw;
+    c.HWp = (TH + 2) * (TW + 2);
+    c.PPX = TH * TW;
+    c.PB = t.bm / c.PPX;
+    c.HR = c.PB * c.HWp;
+    const int rpp = gemm_halo_dma_threads(tile) / 8;
+    c.APASS = (c.HR + rpp - 1) / rpp;
+    c.npx = p.Wd / TW;
+    c.npy = p.H / TH;
+    c.pimg = c.npx * c.npy;
+    c.npatch = p.M / c.PPX;
+    c.inv_hwp = inv(c.HWp); c.inv_tw2 = inv(TW + 2); c.inv_pimg = inv(c.pimg);
+    c.inv_npx = inv(c.npx); c.inv_ppx = inv(c.PPX); c.inv_tw = inv(TW);
+    c.nbm = (c.npatch + c.PB - 1) / c.PB;
+    c.nk = p.Cin / 64;
+  } else {
+    c.nbm = (p.M + t.bm - 1) / t.bm;
+    c.nk = p.K / 64;
+  }
+  c.nbn = (p.N + t.bn - 1) / t.bn;
+  c.nblk = c.nbm * c.nbn;
+  c.xq = c.nblk >> 3;
+  c.xr = c.nblk & 7;
+  c.gm = (p.gm <= 0 || p.gm >= c.nbm) ? std::max(c.nbm, 1) : p.gm;
+  const int last = c.nbm % c.gm;
+  c.per = gemm_magic(c.gm * c.nbn); c.rows = gemm_magic(c.gm); c.last = gemm_magic(last ? last : c.gm);
+  c.kper = (c.nk + sk - 1) / sk;
+  c.n2tot = p.Cin2 / 64;
+  c.used = c.kper > 0 ? (c.nk + c.kper - 1) / c.kper : 1;
+  c.per2 = (c.n2tot + std::max(c.used, 1) - 1) / std::max(c.used, 1);
+  c.wrb = gemm_magic(p.w_rows > 0 ? p.w_rows / t.bm : 0);
+  c.ohw = gemm_magic(std::max(p.OH * p.OW, 1));
+  c.ow = gemm_magic(std::max(p.OW, 1));
+  c.cin = gemm_magic(std::max(p.Cin, 1));
+  *out = c;
+}
+
 bool gemm_split_worth_tuning(const GemmParams& p, int tile, int splitk) {
   if (splitk <= 1) return true;
   return gemm_tile_is_halo(tile) ? p.Cin / 64 / splitk >= 1 : p.K / 64 / splitk >= 2;
@@ -343,19 +400,20 @@ hipError_t launch_gemm(const GemmParams& p, int tile_cfg, int batch, hipStream_t
   const int part = kGemmTiles[tile_cfg].part;
   hipError_t e;
   if (r.family == DF_FAM_PGEGLU) return launch_gemm_pgeglu(tile_cfg, p, stream);
-  if (r.family == DF_FAM_WGEGLU) return launch_gemm_wgeglu(tile_cfg, p, stream);
+  GemmParams q = p;        // what the kernels get: the problem + the launch constants (+ the halo tiles' patch)
+  gemm_launch_consts(p, tile_cfg, p.splitk, r, &q.lc);
+  if (r.family == DF_FAM_WGEGLU) return launch_gemm_wgeglu(tile_cfg, q, stream);
   if (r.family == DF_FAM_HALO) {
-    GemmParams q = p;
     q.th = r.th; q.tw = r.tw; q.halo_ring_bytes = r.halo_ring_bytes;
     e = launch_gemm_halo(tile_cfg, r.epi, q, r.zdim, r.lds, stream);
-  } else if (r.family == DF_FAM_PS) e = part ? launch_gemm_ps_small(r.mode, tile_cfg, r.epi, p, r.zdim, stream) : launch_gemm_ps(r.mode, tile_cfg, r.epi, p, r.zdim, stream);
-  else if (r.mode == 0) e = part ? launch_gemm_m0b(tile_cfg, r.epi, p, r.zdim, stream) : launch_gemm_m0a(tile_cfg, r.epi, p, r.zdim, stream);
-  else if (r.mode == 1) e = launch_gemm_m1(tile_cfg, r.epi, p, r.zdim, stream);
-  else if (r.mode == 2) e = launch_gemm_m2(tile_cfg, r.epi, p, r.zdim, stream);
-  else e = launch_gemm_m3(tile_cfg, r.epi, p, r.zdim, stream);
+  } else if (r.family == DF_FAM_PS) e = part ? launch_gemm_ps_small(r.mode, tile_cfg, r.epi, q, r.zdim, stream) : launch_gemm_ps(r.mode, tile_cfg, r.epi, q, r.zdim, stream);
+  else if (r.mode == 0) e = part ? launch_gemm_m0b(tile_cfg, r.epi, q, r.zdim, stream) : launch_gemm_m0a(tile_cfg, r.epi, q, r.zdim, stream);
+  else if (r.mode == 1) e = launch_gemm_m1(tile_cfg, r.epi, q, r.zdim, stream);
+  else if (r.mode == 2) e = launch_gemm_m2(tile_cfg, r.epi, q, r.zdim, stream);
+  else e = launch_gemm_m3(tile_cfg, r.epi, q, r.zdim, stream);
   if (e != hipSuccess || r.reduce == DF_RED_NONE || r.reduce == DF_RED_DEFERRED) return e;
   if (r.mode != 3) return launch_splitk_reduce(p, r.reduce, stream);
-  GemmParams q = p;
+  q = p;
   q.M = 4 * p.M;           // the slabs hold the x2 output map
   q.taps = 1;
   return launch_splitk_reduce(q, r.reduce, stream);

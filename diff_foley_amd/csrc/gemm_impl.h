@@ -526,12 +526,20 @@ __device__ __forceinline__ void wait_vmcnt() {
 // division: q = trunc((x + 0.5) * (1/d)) is exact for 0 <= x < 2^22 (the product's error (q+1) 2^-23 stays below the 0.5/d
 // distance of (x + 0.5)/d from the next integer).  The kernels' prologues turn tile rows into (sample, y, x) with up to 60 such
 // divisions per thread before the first operand request can be issued -- ~3 us of the ~4.4 us launch floor of a halo conv.
+// Every divisor is a constant of the launch, so the reciprocal -- an IEEE division, ~40 instructions -- comes from the host
+// (GemmLaunch, gemm.h): inv_ = 1.0f / (float)d_.
 struct FastDiv {
   float inv;
   int d;
-  __device__ __forceinline__ explicit FastDiv(int d_) : inv(1.0f / (float)d_), d(d_) {}
+  __device__ __forceinline__ FastDiv(int d_, float inv_) : inv(inv_), d(d_) {}
   __device__ __forceinline__ int div(int x) const { return (int)(((float)x + 0.5f) * inv); }
 };
+// x / m.d for 0 <= x < 2^31 by multiply-high with the host's magic number (gemm_magic, gemm.hip).  A block-uniform x stays on the
+// scalar unit (s_mul_hi_u32), which FastDiv's float arithmetic cannot: the quotient -- tile origins, operand bases and buffer
+// resources are computed from it -- would live in vector registers, and a buffer request whose resource does becomes a loop.
+__device__ __forceinline__ int magic_div(int x, const GemmMagic& m) {
+  return m.d == 1 ? x : (int)(__umulhi((unsigned)x, m.mul) >> m.sh);
+}
 
 // Logical tile id -> (M tile, N tile): M-fastest inside row groups of `gm` M-tiles (gm <= 0: one group = plain M-fastest).
 __device__ __forceinline__ void tile_of(int lid, int nbm, int nbn, int gm, int& mt, int& nt) {
@@ -544,6 +552,18 @@ __device__ __forceinline__ void tile_of(int lid, int nbm, int nbn, int gm, int& 
   const int rows = min(gm, nbm - grp * gm);
   nt = rem / rows;
   mt = grp * gm + (rem - nt * rows);
+}
+// The same map from the launch constants, with the XCD remap in front of it (block b runs on XCD b % 8; each XCD gets a contiguous
+// range of logical tiles): no division -- c.gm is normalised to 1 .. nbm, a row group is full (c.gm M tiles) or the short last one,
+// and the two quotients are multiply-highs by the host's magic numbers, on the scalar unit.
+__device__ __forceinline__ void tile_of_lc(const GemmLaunch& c, int bid, int& mt, int& nt) {
+  const int xcd = bid & 7, idx = bid >> 3;
+  const int lid = (xcd < c.xr ? xcd * (c.xq + 1) : c.xr * (c.xq + 1) + (xcd - c.xr) * c.xq) + idx;
+  const int grp = magic_div(lid, c.per), rem = lid - grp * c.per.d;
+  const bool full = c.nbm - grp * c.gm >= c.gm;
+  const GemmMagic rows = full ? c.rows : c.last;
+  nt = magic_div(rem, rows);
+  mt = grp * c.gm + (rem - nt * rows.d);
 }
 
 // NSTB = depth of the W ring when it differs from the A ring's NST ("deep weight ring" tiles for the weight-streaming layers):
@@ -611,17 +631,11 @@ __device__ __forceinline__ void gemm_bf16_body(const GemmParams& p) {
   };
   stamp();
   // ---- tile id with XCD-aware remap (block b runs on XCD b%8; give each XCD a contiguous range)
-  const int nbm = (p.M + BM - 1) / BM, nbn = (p.N + BN - 1) / BN;
-  const int nblk = nbm * nbn;
-  int lid;
-  {
-    const int bid = blockIdx.x, q = nblk >> 3, r = nblk & 7, xcd = bid & 7, idx = bid >> 3;
-    lid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
   // each XCD owns a contiguous range of logical tiles, walked M-fastest inside row groups of p.gm M-tiles: the walk
   // decides which A / W panels the XCD's 4 MB L2 gets to share (a miss is served by MALL at ~1/5 of the L2 rate)
+  const GemmLaunch& lc = p.lc;      // tile counts, the walk, the K range of a split: from the host (gemm.h), nothing is divided here
   int mt_, nt_;
-  tile_of(lid, nbm, nbn, p.gm, mt_, nt_);
+  tile_of_lc(lc, blockIdx.x, mt_, nt_);
   const int m0 = mt_ * BM, n0 = nt_ * BN;
 
   // LayerNorm folded into this GEMM: thread r < BM requests the producer's per-row (sum, sumsq) partials of tile row r FIRST
@@ -645,16 +659,16 @@ __device__ __forceinline__ void gemm_bf16_body(const GemmParams& p) {
   // phase + 4 * split, one weight matrix per phase
   const int phase = (MODE == 3) ? (z & 3) : 0;
   if (MODE == 3) z >>= 2;
-  const int nk = p.K / BK;
+  const int nk = lc.nk;
   int kt0 = 0, kt1 = nk, batch = (MODE == 3) ? phase : z;
   if (p.splitk > 1) {
-    const int per = (nk + p.splitk - 1) / p.splitk;
-    kt0 = z * per;
-    kt1 = min(nk, kt0 + per);
+    kt0 = z * lc.kper;
+    kt1 = min(nk, kt0 + lc.kper);
     if (MODE != 3) batch = 0;
   }
   const bf16_t* Ab = p.A + (long)batch * p.a_bs;
-  const bf16_t* Wb = p.W + (long)batch * p.w_bs + (p.w_rows > 0 ? (long)(m0 / p.w_rows) * p.w_bs : 0l);
+  // per-sample weights: w_rows is a whole number of M tiles, m0 / w_rows = mt / (w_rows / BM)
+  const bf16_t* Wb = p.W + (long)batch * p.w_bs + (lc.wrb.d > 0 ? (long)magic_div(mt_, lc.wrb) * p.w_bs : 0l);
 
   // ---- per-thread staging coordinates: chunk c (8 bf16 = 16 B) of rows (tid>>3) + 32*i.
   // Operands are fetched with raw buffer loads: an out-of-range byte offset (OOB) makes the hardware return
@@ -670,14 +684,62 @@ __device__ __forceinline__ void gemm_bf16_body(const GemmParams& p) {
   const unsigned k1b = (MODE == 0 && p.Cin2 > 0) ? (unsigned)(p.K - p.Cin2) * 2u : 0xffffffffu;
   const int r0 = tid >> 3;
   const int c8 = ((tid & 7) ^ ((r0 >> 1) & 7)) * 8;   // source chunk that lands in LDS slot (tid&7) of row r0+32i
+  typedef __attribute__((address_space(3))) void* lds_ptr;
+  const int nt = (p.dbg & 4) ? 0 : kt1 - kt0;
+  // ---- the weight side first.  A weight request needs the tile id, the thread id and K -- none of the row arithmetic below -- and
+  // the weights come cold from HBM every step: in the conv MODEs (WFIRST) the prologue's weight tiles are requested HERE, so their
+  // latency covers the row -> (sample, y, x) decomposition instead of following it.  (MODE 0 has no row arithmetic worth covering
+  // and keeps the per-tile order [A(t), W(t)] of the steady state.)
+  constexpr bool WFIRST = MODE != 0;
+  // (32-bit arithmetic: an offset is the low 32 bits of the product either way)
+  unsigned b_off[BP];
+#pragma unroll
+  for (int i = 0; i < BP; ++i) {
+    const int n = n0 + r0 + RPP * i;
+    b_off[i] = (n < p.N) ? ((unsigned)n * (unsigned)p.K + (unsigned)c8) * 2u : OOB;
+  }
+  char* const dmaB = smem + NST * BM * BK * 2 + wid * (8 * BK * 2);
+  // weight tile TW into the W ring's running write slot (deep-ring tiles only)
+  int w_wr = 0, w_rd = 0;        // byte offsets of the W ring's write / read slot
+#define DF_DMA_W(TW)                                                                              \
+  {                                                                                             \
+    const unsigned kbw = ((TW) < nt) ? ((p.dbg & 1) ? 0u : (unsigned)(kt0 + (TW)) * (BK * 2)) : OOB; \
+    _Pragma("unroll") for (int i = 0; i < BP; ++i)                                              \
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (lds_ptr)(dmaB + w_wr + i * RPP * (BK * 2)), 16, \
+                                               b_off[i] + kbw, 0, 0, 0);                        \
+    w_wr += WSLOT;                                                                              \
+    if (w_wr == NSTB * WSLOT) w_wr = 0;                                                         \
+  }
+  // the weight rows that go with activation tile T: tile T into ring slot ST, or (deep weight ring) tile T + WD into the running slot
+#define DF_DMA_B(T, ST)                                                                           \
+  {                                                                                             \
+    if constexpr (WD == 0) {                                                                    \
+      const unsigned kb = ((T) < nt) ? ((p.dbg & 1) ? 0u : (unsigned)(kt0 + (T)) * (BK * 2)) : OOB; \
+      _Pragma("unroll") for (int i = 0; i < BP; ++i)                                            \
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (lds_ptr)(dmaB + ((ST) * BN + i * RPP) * (BK * 2)), 16, \
+                                                 b_off[i] + kb, 0, 0, 0);                       \
+    } else {                                                                                    \
+      DF_DMA_W((T) + WD);                                                                       \
+    }                                                                                           \
+  }
+  if constexpr (WD > 0) {     // the weight stream leads: tiles 0 .. WD-1 first, then the pairs [A(i), W(i + WD)] of the steady state
+#pragma unroll
+    for (int tw = 0; tw < WD; ++tw) DF_DMA_W(tw);
+  }
+  if constexpr (WFIRST) {
+    if (!PS || producer) {
+      DF_DMA_B(0, 0);
+      if (NST > 2) DF_DMA_B(1, 1);
+      if (NST > 3) DF_DMA_B(2, 2);
+      if (NST > 4) DF_DMA_B(3, 3);
+    }
+  }
   unsigned a_off[AP];   // MODE 0: byte offset of (row, chunk); MODE 1: byte offset of the centre-tap pixel;
                         // MODE 2: pixel index base n*H*W
   unsigned a_msk[AP];   // MODE 1: bit t set <=> tap t of this row reads inside the image
   unsigned a_off2[AP];  // MODE 1 with a folded skip connection: byte offset of the centre pixel in the second tensor
   int a_iy[AP], a_ix[AP];
   const int UH = p.H << p.ups, UW = p.Wd << p.ups;
-  const bool fast_rows = MODE != 0 && p.M + BM < (1 << 22);      // row -> (sample, y, x) by FastDiv (exact below 2^22)
-  const FastDiv fd_ohw(MODE != 0 ? max(p.OH * p.OW, 1) : 1), fd_ow(MODE != 0 ? max(p.OW, 1) : 1);
 #pragma unroll
   for (int i = 0; i < AP; ++i) {
     const int m = m0 + r0 + RPP * i;
@@ -686,19 +748,12 @@ __device__ __forceinline__ void gemm_bf16_body(const GemmParams& p) {
     a_off2[i] = OOB;
     a_iy[i] = a_ix[i] = 0;
     if (MODE == 0) {
-      a_off[i] = mv ? (unsigned)(((long)m * p.lda + c8) * 2) : OOB;
-      if (p.Cin2 > 0) a_off2[i] = mv ? (unsigned)(((long)m * p.lda2 + c8) * 2) : OOB;
+      a_off[i] = mv ? ((unsigned)m * (unsigned)p.lda + (unsigned)c8) * 2u : OOB;
+      if (p.Cin2 > 0) a_off2[i] = mv ? ((unsigned)m * (unsigned)p.lda2 + (unsigned)c8) * 2u : OOB;
     } else {
-      const int ohw = p.OH * p.OW;
-      int nb, rem, oy;
-      if (fast_rows) {
-        nb = fd_ohw.div(m); rem = m - nb * ohw;
-        oy = fd_ow.div(rem);
-      } else {
-        nb = m / ohw; rem = m - nb * ohw;
-        oy = rem / p.OW;
-      }
-      const int ox = rem - oy * p.OW;
+      // row -> (sample, y, x): multiply-high by the host's magic numbers, exact for every row index
+      const int nb = magic_div(m, lc.ohw), rem = m - nb * lc.ohw.d;
+      const int oy = magic_div(rem, lc.ow), ox = rem - oy * p.OW;
       if (MODE == 3) {
         // rows = INPUT-resolution pixels (OH = H, OW = Wd here); tap (dy, dx) of phase (a, b) reads pixel (y-1+a+dy, x-1+b+dx)
         const int pa = phase >> 1, pb = phase & 1;
@@ -727,16 +782,7 @@ __device__ __forceinline__ void gemm_bf16_body(const GemmParams& p) {
       }
     }
   }
-  unsigned b_off[BP];
-#pragma unroll
-  for (int i = 0; i < BP; ++i) {
-    const int n = n0 + r0 + RPP * i;
-    b_off[i] = (n < p.N) ? (unsigned)(((long)n * p.K + c8) * 2) : OOB;
-  }
-
-  typedef __attribute__((address_space(3))) void* lds_ptr;
   constexpr int LPT = AP + BP;                  // DMA instructions per wave per K tile
-  const int nt = (p.dbg & 4) ? 0 : kt1 - kt0;
 
   // Request tile T (relative to kt0) into ring slot ST (compile-time): every wave writes 8 rows x 128 B (1 KiB,
   // lane-linear) per instruction.  Tiles past the end are requested out of bounds (zeros land in a dead slot), so
@@ -744,12 +790,12 @@ __device__ __forceinline__ void gemm_bf16_body(const GemmParams& p) {
   int d_tap = 0, d_cc = 0;       // conv: (tap, channel offset) of the NEXT tile to request, advanced incrementally
   if (MODE != 0) {
     const int k0 = kt0 * BK;
-    d_tap = min(k0 / p.Cin, 9);             // tap 9 = the folded skip connection's channel range
+    d_tap = min(magic_div(k0, lc.cin), 9);             // tap 9 = the folded skip connection's channel range
     d_cc = k0 - d_tap * p.Cin;
   }
   char* const dmaA = smem + wid * (8 * BK * 2);
-  char* const dmaB = smem + NST * BM * BK * 2 + wid * (8 * BK * 2);
-#define DF_DMA(T, ST)                                                                             \
+  // the activation rows of tile T; its weight rows are DF_DMA_B's (above)
+#define DF_DMA_A(T, ST)                                                                           \
   {                                                                                             \
     const bool live = (T) < nt;                                                                 \
     const unsigned k0b = (p.dbg & 1) ? 0u : (unsigned)(kt0 + (T)) * (BK * 2);                         \
@@ -804,39 +850,29 @@ __device__ __forceinline__ void gemm_bf16_body(const GemmParams& p) {
         ++d_tap;                                                                                \
       }                                                                                         \
     }                                                                                           \
-    if constexpr (WD == 0) {                                                                    \
-      const unsigned kb = live ? k0b : OOB;                                                     \
-      _Pragma("unroll") for (int i = 0; i < BP; ++i)                                            \
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (lds_ptr)(dmaB + ((ST) * BN + i * RPP) * (BK * 2)), 16, \
-                                                 b_off[i] + kb, 0, 0, 0);                       \
-    } else {   /* deep weight ring: tile T + WD into the running write slot */                  \
-      DF_DMA_W((T) + WD);                                                                       \
-    }                                                                                           \
   }
-  // weight tile TW into the W ring's running write slot (deep-ring tiles only)
-  int w_wr = 0, w_rd = 0;        // byte offsets of the W ring's write / read slot
-#define DF_DMA_W(TW)                                                                              \
-  {                                                                                             \
-    const unsigned kbw = ((TW) < nt) ? ((p.dbg & 1) ? 0u : (unsigned)(kt0 + (TW)) * (BK * 2)) : OOB; \
-    _Pragma("unroll") for (int i = 0; i < BP; ++i)                                              \
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (lds_ptr)(dmaB + w_wr + i * RPP * (BK * 2)), 16, \
-                                               b_off[i] + kbw, 0, 0, 0);                        \
-    w_wr += WSLOT;                                                                              \
-    if (w_wr == NSTB * WSLOT) w_wr = 0;                                                         \
+#define DF_DMA(T, ST) \
+  {                   \
+    DF_DMA_A(T, ST);  \
+    DF_DMA_B(T, ST);  \
   }
 
   // ---- prologue: fill NST-1 ring slots -- as early as the request offsets exist.  Everything below (accumulator init,
   // fragment offsets, epilogue prefetch: ~150-700 instructions) runs while the first tiles are in flight instead of in front of
   // them; the epilogue prefetch's loads are then younger than these requests, which only makes the first ring wait stricter.
-  if constexpr (WD > 0) {     // the weight stream leads: tiles 0 .. WD-1 first, then the pairs [A(i), W(i + WD)] of the steady state
-#pragma unroll
-    for (int tw = 0; tw < WD; ++tw) DF_DMA_W(tw);
-  }
+  // (WFIRST: the weight rows of these tiles were requested above, in front of the row arithmetic.)
   if (!PS || producer) {
-    DF_DMA(0, 0);
-    if (NST > 2) DF_DMA(1, 1);
-    if (NST > 3) DF_DMA(2, 2);
-    if (NST > 4) DF_DMA(3, 3);
+    if constexpr (WFIRST) {
+      DF_DMA_A(0, 0);
+      if (NST > 2) DF_DMA_A(1, 1);
+      if (NST > 3) DF_DMA_A(2, 2);
+      if (NST > 4) DF_DMA_A(3, 3);
+    } else {
+      DF_DMA(0, 0);
+      if (NST > 2) DF_DMA(1, 1);
+      if (NST > 3) DF_DMA(2, 2);
+      if (NST > 4) DF_DMA(3, 3);
+    }
   }
   __builtin_amdgcn_sched_barrier(0);
   stamp();
@@ -936,7 +972,9 @@ __device__ __forceinline__ void gemm_bf16_body(const GemmParams& p) {
     if (producer) {
       // the producer's K loop: request tile it + NST - 1 into the slot tile it - 1 was read from, wait until tile it + 1 has
       // landed (<= NST - 2 younger tiles of this wave in flight), meet the consumers at the K-step barrier
-      wait_vmcnt<(NST - 2) * LPT>();
+      // (WFIRST: the prologue's order is W(0 ..), A(0 ..) -- tile 0 is complete only when A(0) is, and the counted waits of the
+      // loop below hold for the steady order [A(t), W(t)]: drain the prologue once, every later bound then counts loop requests only)
+      wait_vmcnt<WFIRST ? 0 : (NST - 2) * LPT>();
       __builtin_amdgcn_s_barrier();
 #define DF_PITER(ST)                                                                              \
   {                                                                                             \
@@ -1017,7 +1055,11 @@ __device__ __forceinline__ void gemm_bf16_body(const GemmParams& p) {
     }
 #undef DF_FRAGD
   } else {
-  DF_RING_SYNC((NST - 2) * LPT + (WD > 0 ? BP : 0));       // tile 0 landed and visible
+  // tile 0 landed and visible.  WFIRST: the prologue's order is W(0 ..), A(0 ..), so tile 0 is complete only when A(0) is and the
+  // loop's counted waits (steady order [A(t), W(t)]) would be too loose for the tiles behind it: the prologue is drained once
+  // (the requests went out back to back: the later tiles land within a few hundred cycles of the first) and every later bound
+  // counts requests of the loop alone.
+  DF_RING_SYNC(WFIRST ? 0 : (NST - 2) * LPT + (WD > 0 ? BP : 0));
   stamp();
   while (it < nt) {
     DF_ITER(0);
@@ -1203,35 +1245,28 @@ __device__ __forceinline__ void conv3x3_halo_body(const GemmParams& p) {
       reinterpret_cast<unsigned long long*>(p.partial)[(long)blockIdx.x * 32 + n_stamp++] = __builtin_amdgcn_s_memtime();
   };
   stamp();
-  const int TH = p.th, TW = p.tw, HWp = (TH + 2) * (TW + 2), PPX = TH * TW;
-  const int PB = BM / PPX;                      // patches per block
-  const int HR = PB * HWp;                      // halo rows
-  const int APASS = (HR + RPP - 1) / RPP;       // halo passes (block-uniform)
+  const GemmLaunch& lc = p.lc;                  // the patch geometry, tile walk and split ranges: from the host (gemm.h)
+  const int TH = p.th, TW = p.tw, HWp = lc.HWp, PPX = lc.PPX;
+  const int PB = lc.PB;                         // patches per block
+  const int HR = lc.HR;                         // halo rows
+  const int APASS = lc.APASS;                   // halo passes (block-uniform)
   const int HRP = APASS * RPP;
   bf16_t* sA = reinterpret_cast<bf16_t*>(smem);                 // [2][HRP][64]
   bf16_t* sW = sA + 2 * HRP * BK;                               // [NSTW][max(BN,RPP)][64]
   constexpr int WROWS = WPASS * RPP;
 
-  const int npx = p.Wd / TW, npy = p.H / TH;    // patches per image
-  const int npatch = (p.M / PPX);               // total patches (M = NB*H*W)
-  const int nbm = (npatch + PB - 1) / PB, nbn = (p.N + BN - 1) / BN;
-  const int nblk = nbm * nbn;
-  int lid;
-  {
-    const int bid = blockIdx.x, q = nblk >> 3, r = nblk & 7, xcd = bid & 7, idx = bid >> 3;
-    lid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int npx = lc.npx, npimg = lc.pimg;      // patches per image row / per image
+  const int npatch = lc.npatch;                 // total patches (M = NB*H*W)
   int mt, nt_;
-  tile_of(lid, nbm, nbn, p.gm, mt, nt_);
+  tile_of_lc(lc, blockIdx.x, mt, nt_);
   const int n0 = nt_ * BN;
 
   const int z = blockIdx.z;
-  const int nchunk = p.Cin / BK;
+  const int nchunk = lc.nk;
   int c0 = 0, c1 = nchunk;
   if (p.splitk > 1) {
-    const int per = (nchunk + p.splitk - 1) / p.splitk;
-    c0 = z * per;
-    c1 = min(nchunk, c0 + per);
+    c0 = z * lc.kper;
+    c1 = min(nchunk, c0 + lc.kper);
   }
   const int nc = max(c1 - c0, 0);
   // ResBlock skip connection folded into conv2 (openai_unetmodel.py:234-241, 275: skip(x) + h): a TAIL of n2 one-tap K steps after
@@ -1239,14 +1274,11 @@ __device__ __forceinline__ void conv3x3_halo_body(const GemmParams& p) {
   // tiles only, round 5).  With split-K the skip slices are dealt to the splits that own conv slices, in the same order.
   int s0 = 0, n2 = 0;
   if (PS != 0 && p.Cin2 > 0) {
-    const int n2tot = p.Cin2 / BK;
     if (p.splitk > 1) {
-      const int per = (nchunk + p.splitk - 1) / p.splitk, used = (nchunk + per - 1) / per;
-      const int per2 = (n2tot + used - 1) / used;
-      s0 = z * per2;
-      n2 = (z < used) ? max(min(n2tot, s0 + per2) - s0, 0) : 0;
+      s0 = z * lc.per2;
+      n2 = (z < lc.used) ? max(min(lc.n2tot, s0 + lc.per2) - s0, 0) : 0;
     } else {
-      n2 = n2tot;
+      n2 = lc.n2tot;
     }
   }
   const int nc9 = nc * 9;
@@ -1266,8 +1298,34 @@ __device__ __forceinline__ void conv3x3_halo_body(const GemmParams& p) {
   // conflict-free for TW = 16 (SC = 0) and TW = 8 (SC = 4) at every tap shift.
   const int SC = (TW == 16) ? 0 : 4;
   // all quotients below are of values < 2^22 (gemm_route checks the patch count): FastDiv instead of 32-bit division
-  const FastDiv fd_hwp(HWp), fd_tw2(TW + 2), fd_pimg(npy * npx), fd_npx(npx), fd_ppx(PPX), fd_tw(TW);
+  const FastDiv fd_hwp(HWp, lc.inv_hwp), fd_tw2(TW + 2, lc.inv_tw2), fd_pimg(npimg, lc.inv_pimg), fd_npx(npx, lc.inv_npx),
+      fd_ppx(PPX, lc.inv_ppx), fd_tw(TW, lc.inv_tw);
   constexpr int MAXAP = 12;
+  // ---- prologue, first half: W(0 .. NSTW-2).  A weight request needs the tile id, the thread id and K -- nothing of the halo-row
+  // table below, nor its barrier -- and the weights come cold from HBM every step (1.7 GB of them against 256 MB of Infinity
+  // Cache): requested here, their latency covers the table instead of following it.
+  unsigned w_off[WPASS];
+#pragma unroll
+  for (int i = 0; i < WPASS; ++i) {
+    const int n = n0 + r0 + RPP * i;
+    w_off[i] = (n < p.N && r0 + RPP * i < BN) ? ((unsigned)n * (unsigned)p.K + (unsigned)c8) * 2u : OOB;
+  }
+  // weights of iteration IT (= slice*9 + tap, relative to c0) into ring slot ST
+#define DF_HALO_W(IT, ST)                                                                         \
+  {                                                                                             \
+    bf16_t* w_ = sW + (ST) * WROWS * BK + wid * (8 * BK);                                       \
+    const int cs_ = (IT) / 9, tp_ = (IT) - cs_ * 9;                                             \
+    const bool live = (IT) < nc9 + n2;          /* (IT) >= nc9: weight tile of step (IT) - nc9 of the folded-skip tail */ \
+    const unsigned kb = (IT) < nc9 ? (unsigned)(tp_ * p.Cin + (c0 + cs_) * BK) * 2u             \
+                                   : (unsigned)(9 * p.Cin + (s0 + (IT) - nc9) * BK) * 2u;      \
+    _Pragma("unroll") for (int i = 0; i < WPASS; ++i)                                           \
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (lds_ptr)(w_ + i * RPP * BK), 16,           \
+                                               (live && w_off[i] != OOB) ? w_off[i] + kb : OOB, 0, 0, 0); \
+  }
+  if (!PS || producer) {
+#pragma unroll
+    for (int t = 0; t < NSTW - 1; ++t) DF_HALO_W(t, t);
+  }
   // Halo row -> source pixel, ONE decomposition per halo row of the block (round 4): every thread of the block (both roles)
   // resolves the rows hr = thread, thread + block, ... into a table entry (byte offset of the pixel's channel 0 | 3-bit swizzle
   // key, or ~0 outside the image) in LDS behind the ring; the requesting threads then pick up their <= 12 rows with one ds_read
@@ -1280,7 +1338,7 @@ __device__ __forceinline__ void conv3x3_halo_body(const GemmParams& p) {
     const int g = mt * PB + pi;                  // global patch id
     unsigned e = 0xffffffffu;
     if (g < npatch) {
-      const int n = fd_pimg.div(g), gr = g - n * (npy * npx);
+      const int n = fd_pimg.div(g), gr = g - n * npimg;
       const int gy = fd_npx.div(gr), gx = gr - gy * npx;
       const int y = gy * TH + hy - 1, x = gx * TW + hx - 1;
       if ((unsigned)y < (unsigned)p.H && (unsigned)x < (unsigned)p.Wd)
@@ -1304,12 +1362,6 @@ __device__ __forceinline__ void conv3x3_halo_body(const GemmParams& p) {
     }
     a_off[i] = off;
   }
-  unsigned w_off[WPASS];
-#pragma unroll
-  for (int i = 0; i < WPASS; ++i) {
-    const int n = n0 + r0 + RPP * i;
-    w_off[i] = (n < p.N && r0 + RPP * i < BN) ? (unsigned)(((long)n * p.K + c8) * 2) : OOB;
-  }
 
   // DMA helpers -------------------------------------------------------------------------------------------------
   // A halo of channel slice C (absolute slice index) into buffer BUF
@@ -1323,21 +1375,9 @@ __device__ __forceinline__ void conv3x3_halo_body(const GemmParams& p) {
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_ptr)(a_ + i * RPP * BK), 16,         \
                                                  (live && a_off[i] != OOB) ? a_off[i] + cb : OOB, 0, 0, 0); \
   }
-  // weights of iteration IT (= slice*9 + tap, relative to c0) into ring slot ST
-#define DF_HALO_W(IT, ST)                                                                         \
-  {                                                                                             \
-    bf16_t* w_ = sW + (ST) * WROWS * BK + wid * (8 * BK);                                       \
-    const int cs_ = (IT) / 9, tp_ = (IT) - cs_ * 9;                                             \
-    const bool live = (IT) < nc9 + n2;          /* (IT) >= nc9: weight tile of step (IT) - nc9 of the folded-skip tail */ \
-    const unsigned kb = (IT) < nc9 ? (unsigned)(tp_ * p.Cin + (c0 + cs_) * BK) * 2u             \
-                                   : (unsigned)(9 * p.Cin + (s0 + (IT) - nc9) * BK) * 2u;      \
-    _Pragma("unroll") for (int i = 0; i < WPASS; ++i)                                           \
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (lds_ptr)(w_ + i * RPP * BK), 16,           \
-                                               (live && w_off[i] != OOB) ? w_off[i] + kb : OOB, 0, 0, 0); \
-  }
 
-  // ---- prologue: A(0), W(0 .. NSTW-2) -- requested as soon as the offsets exist; fragment coordinates, accumulator init and
-  // the epilogue prefetch below run while these are in flight
+  // ---- prologue, second half: A(0), as soon as its offsets exist; fragment coordinates, accumulator init and the epilogue
+  // prefetch below run while it and W(0 .. NSTW-2) are in flight
   // PS: the first halo is the longest request burst of the block (<= 12 per wavefront in front of the first MFMA) and the consumers
   // have nothing to do yet: they take its odd passes (own vmcnt(0) in front of the first tap barrier), the producers the even ones.
 #define DF_HALO_A_PAR(C, BUF, PAR)                                                                \
@@ -1352,15 +1392,11 @@ __device__ __forceinline__ void conv3x3_halo_body(const GemmParams& p) {
   if constexpr (PS != 0) {
     if (producer) {
       DF_HALO_A_PAR(c0, 0, 0);
-#pragma unroll
-      for (int t = 0; t < NSTW - 1; ++t) DF_HALO_W(t, t);
     } else {
       DF_HALO_A_PAR(c0, 0, 1);
     }
   } else {
     DF_HALO_A(c0, 0);
-#pragma unroll
-    for (int t = 0; t < NSTW - 1; ++t) DF_HALO_W(t, t);
   }
 #undef DF_HALO_A_PAR
   __builtin_amdgcn_sched_barrier(0);
@@ -1392,7 +1428,7 @@ __device__ __forceinline__ void conv3x3_halo_body(const GemmParams& p) {
     const int pi = fd_ppx.div(rr), rem = rr - pi * PPX;
     const int y = fd_tw.div(rem), x = rem - y * TW;
     const int g = mt * PB + pi;
-    const int n = fd_pimg.div(g), gr = g - n * (npy * npx);
+    const int n = fd_pimg.div(g), gr = g - n * npimg;
     const int gy = fd_npx.div(gr), gx = gr - gy * npx;
     return (g < npatch) ? (n * p.H + gy * TH + y) * p.Wd + gx * TW + x : p.M;
   };
@@ -1403,7 +1439,9 @@ __device__ __forceinline__ void conv3x3_halo_body(const GemmParams& p) {
     if (producer) {
       // producer K loop: per tap, the weight request NSTW - 1 taps ahead (+ at tap 0 the next slice's halo), the counted wait for
       // the next tap's operands -- DF_HALO_SYNC's rule, the issue order is the symmetric kernel's -- and the tap barrier
-      wait_vmcnt<(NSTW - 2) * WPASS>();
+      // (the prologue's order is W(0 .. NSTW-2), A(0): tap 0 needs the halo, its youngest request -- everything of the prologue has
+      // landed at the first tap barrier, and every counted wait below counts requests of the loop alone, whose order is unchanged)
+      wait_vmcnt<0>();
       __builtin_amdgcn_s_barrier();
       // The next slice's halo is requested in pieces, pass i with tap i % 8, IN FRONT of that tap's weight request (round 4,
       // tools/halo_stamps.py: issued whole at tap 0, its <= 12 requests per wavefront at ~130 cycles each made tap 0 cost 1.7 k
@@ -1578,7 +1616,9 @@ __device__ __forceinline__ void conv3x3_halo_body(const GemmParams& p) {
   }
 
   stamp();
-  if constexpr (PS != 0) wait_vmcnt<0>();      // this consumer's share of the first halo
+  // the first halo is the YOUNGEST request of the prologue (weights first): all of it has landed at the first tap barrier (PS: this
+  // consumer's share of the first halo), and the counted waits of the taps count requests of the loop alone
+  wait_vmcnt<0>();
   DF_HALO_SYNC(0);
   stamp();
   for (int cs = 0; cs < nc; ++cs) {
@@ -1659,7 +1699,6 @@ __device__ __forceinline__ void conv3x3_halo_body(const GemmParams& p) {
 // The launch templates only launch: whether (p, tile, split-K) may run, and how, is gemm_route's (gemm.hip).
 template <int BM, int BN, int WGM, int WGN, int NST, int MODE, int EPI, int NSTB = NST, int PS = 0>
 hipError_t launch_cfg(const GemmParams& p, int zdim, hipStream_t stream) {
-  const int nbm = (p.M + BM - 1) / BM, nbn = (p.N + BN - 1) / BN;
   constexpr size_t ring = ((size_t)BM * NST + (size_t)BN * NSTB) * BK * 2;     // operand rings (A: NST slots, W: NSTB slots)
   constexpr size_t stage = (size_t)BM * (BN + 4) * 4 + (size_t)BM * 8 + (MODE == 3 ? (size_t)BM * 4 : 0);   // epilogue tile + (mean, rstd) row table (+ MODE 3 pixel table)
   constexpr size_t lds = ring > stage ? ring : stage;
@@ -1672,12 +1711,12 @@ hipError_t launch_cfg(const GemmParams& p, int zdim, hipStream_t stream) {
     if (e != hipSuccess) return e;
     attr_set = true;
   }
-  hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, WGM, WGN, NST, MODE, EPI, NSTB, PS>), dim3(nbm * nbn, 1, MODE == 3 ? 4 * zdim : zdim),
+  hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, WGM, WGN, NST, MODE, EPI, NSTB, PS>), dim3(p.lc.nblk, 1, MODE == 3 ? 4 * zdim : zdim),
                      dim3(64 * WGM * WGN * (1 + PS)), lds, stream, p);
   return hipGetLastError();
 }
 
-// p.th / p.tw / p.halo_ring_bytes and lds come from the route
+// p.th / p.tw / p.halo_ring_bytes, p.lc and lds come from the route
 template <int BM, int BN, int WGM, int WGN, int NSTW, int EPI, int PS = 0>
 hipError_t launch_halo(const GemmParams& p, int zdim, size_t lds, hipStream_t stream) {
   static size_t attr = 0;
@@ -1687,9 +1726,7 @@ hipError_t launch_halo(const GemmParams& p, int zdim, size_t lds, hipStream_t st
     if (e != hipSuccess) return e;
     attr = lds;
   }
-  const int ppx = p.th * p.tw, PB = BM / ppx;
-  const int nbm = (p.M / ppx + PB - 1) / PB, nbn = (p.N + BN - 1) / BN;
-  hipLaunchKernelGGL((conv3x3_halo_kernel<BM, BN, WGM, WGN, NSTW, EPI, PS>), dim3(nbm * nbn, 1, zdim), dim3(64 * WGM * WGN * (1 + PS)), lds,
+  hipLaunchKernelGGL((conv3x3_halo_kernel<BM, BN, WGM, WGN, NSTW, EPI, PS>), dim3(p.lc.nblk, 1, zdim), dim3(64 * WGM * WGN * (1 + PS)), lds,
                      stream, p);
   return hipGetLastError();
 }

@@ -53,6 +53,20 @@ class GemmTile(C.Structure):
     _fields_ = [("size", C.c_int64), ("name", C.c_char_p)] + [(n, C.c_int) for n in ("family", "bm", "bn", "dma_threads", "ring", "modes")]
 
 
+class GemmLaunch(C.Structure):
+    """include/df_engine.h df_test_gemm_launch: the launch constants launch_gemm hands a GEMM-family kernel (csrc/gemm.h GemmLaunch)."""
+    class Magic(C.Structure):
+        """x // d == (x * mul) >> (32 + sh) for 0 <= x < 2^31; d == 1: x"""
+        _fields_ = [("mul", C.c_uint32), ("sh", C.c_int), ("d", C.c_int)]
+
+    MAGIC = ("per", "rows", "last", "wrb", "ohw", "ow", "cin")      # what magic[i] divides by (include/df_engine.h)
+    _fields_ = ([("size", C.c_int64)] + [(n, C.c_int) for n in ("nbm", "nbn", "nblk", "xq", "xr", "gm")] + [("magic", Magic * 7)] +
+                [(n, C.c_int) for n in ("nk", "kper", "n2tot", "used", "per2")] +
+                [(n, C.c_int) for n in ("HWp", "PPX", "PB", "HR", "APASS", "npx", "npy", "pimg", "npatch")] +
+                [(n, C.c_float) for n in ("inv_hwp", "inv_tw2", "inv_pimg", "inv_npx", "inv_ppx", "inv_tw")] +
+                [("th", C.c_int), ("tw", C.c_int)])
+
+
 TILE_FAMILIES = ("generic", "halo", "ps", "pgeglu", "wgeglu", "retired")      # df_test_gemm_tile.family
 
 
@@ -209,6 +223,7 @@ _SIGS = {
     "df_test_gemm_why": [C.POINTER(GemmDesc), C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int],
     "df_test_gemm_key": [C.POINTER(GemmDesc), C.c_int, C.c_char_p, C.c_int],
     "df_test_gemm_tile_info": [C.c_int, C.POINTER(GemmTile)],
+    "df_test_gemm_launch_constants": [C.POINTER(GemmDesc), C.c_int, C.c_int, C.c_int, C.POINTER(GemmLaunch)],
     "df_test_xattn_chain": [C.c_void_p] * 10 + [C.c_int] * 6 + [C.c_void_p] * 10 + [C.c_int, C.c_int, C.c_void_p],
     "df_test_pack_ffproj": [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p],
     "df_test_softmax_rows": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p],

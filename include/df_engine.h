@@ -512,6 +512,22 @@ typedef struct df_test_gemm_tile {
   int family, bm, bn, dma_threads, ring, modes;
 } df_test_gemm_tile;
 int df_test_gemm_tile_info(int tile, df_test_gemm_tile* out);
+/* The launch constants launch_gemm hands a GEMM-family kernel for (d, tile, batch, splitk): csrc/gemm.h GemmLaunch (the kernels'
+ * prologues divide by nothing; these are the quotients, the multiply-high magic numbers -- x / d == umulhi(x, mul) >> sh, d == 1: x --
+ * and the FastDiv reciprocals 1.0f / (float)divisor they read), + the halo tiles' patch th x tw.  magic[]: by the tiles of a full row
+ * group (gm nbn), by gm, by the M tiles of the last row group, by w_rows / BM (d 0 = off), by OH OW, by OW, by Cin.  `size` must be
+ * sizeof(df_test_gemm_launch).  Returns 0, 2 when launch_gemm refuses the problem, -1 for a malformed descriptor (message in
+ * df_last_error either way).  Host only. */
+typedef struct df_test_gemm_launch {
+  int64_t size;
+  int nbm, nbn, nblk, xq, xr, gm;
+  struct { uint32_t mul; int sh, d; } magic[7];
+  int nk, kper, n2tot, used, per2;
+  int HWp, PPX, PB, HR, APASS, npx, npy, pimg, npatch;
+  float inv_hwp, inv_tw2, inv_pimg, inv_npx, inv_ppx, inv_tw;
+  int th, tw;
+} df_test_gemm_launch;
+int df_test_gemm_launch_constants(const df_test_gemm_desc* d, int tile, int batch, int splitk, df_test_gemm_launch* out);
 /* The folded cross-attention of one SpatialTransformer (engine_builder.hip context_px, st.xs, st.xo), every intermediate out: ctx [NB*Tc][Dc]
  * and Wkv [2C][Dc] (to_k | to_v) operand type; Wq [C][C], gamma (norm2), bq = Wq . beta fp32; Wo [C][C] operand, bo fp32; x fp32
  * [NB*T][C], xb its operand copy, xstats float2 [NB*T][C/64] (sum, sum of squares per 64 columns).  Outputs: kv [NB*Tc][2C],
