@@ -70,6 +70,10 @@ static void need_positive(const char* what, std::initializer_list<std::pair<cons
   for (auto& d : dims)
     if (d.second <= 0) fail("%s: %s = %ld (empty input: every size must be positive)", what, d.first, d.second);
 }
+static void need_pointers(const char* what, std::initializer_list<std::pair<const char*, const void*>> ptrs) {
+  for (auto& p : ptrs)
+    if (!p.second) fail("%s: %s is a null pointer", what, p.first);
+}
 
 int df_abi_version(void) { return 1; }
 const char* df_operand_dtype(void) {
@@ -564,6 +568,9 @@ int df_mel_to_stft(const float* mel, int B, int n_mels, int T, const float* A, c
                    int iters, float* S, void* stream) {
   return guard([&] {
     need_positive("mel_to_stft", {{"clips", B}, {"mel bins", n_mels}, {"frames", T}});
+    if (n_mels > 128) fail("mel_to_stft: n_mels = %d (the kernel's span tables hold at most 128 rows)", n_mels);
+    if (iters < 0) fail("mel_to_stft: iters = %d (a count of FISTA iterations, 0 or more)", iters);
+    need_pointers("mel_to_stft", {{"mel", mel}, {"A", A}, {"At", At}, {"Pt", Pt}, {"S", S}});
     HIPCHK(launch_mel_to_stft(mel, B, n_mels, T, A, At, Pt, inv_L, iters, S, (hipStream_t)stream));
   });
 }
@@ -572,6 +579,11 @@ int df_griffinlim(const float* S, const float* phase0, int B, int T, int n_iter,
                   void* stream) {
   return guard([&] {
     need_positive("griffinlim", {{"clips", B}, {"frames", T}});
+    if (T < 2) fail("griffinlim: T = %d (one frame is zero hops of audio: at least 2 frames)", T);
+    if (n_iter < 0) fail("griffinlim: n_iter = %d (a count of iterations, 0 or more)", n_iter);
+    if (!(momentum >= 0.f && momentum < 1.f)) fail("griffinlim: momentum = %g (expected 0 <= momentum < 1)", (double)momentum);
+    need_pointers("griffinlim", {{"S", S}, {"phase0", phase0}, {"twiddles", twiddles}, {"window", window}, {"wss", wss},
+                                 {"angles", angles}, {"reb0", reb0}, {"reb1", reb1}, {"frames", frames}, {"wav", wav}});
     HIPCHK(launch_griffinlim(S, phase0, B, T, n_iter, momentum, (const float2*)twiddles, window, wss, (float2*)angles,
                              (float2*)reb0, (float2*)reb1, frames, wav, (hipStream_t)stream));
   });

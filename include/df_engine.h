@@ -202,7 +202,11 @@ int df_frames_to_tensor(const uint8_t* frames_dev, float* out_dev, uint8_t* tmp_
  * df_griffinlim: librosa.griffinlim(S, hop_length=256): 32 fast Griffin-Lim iterations, momentum 0.99; phase0
  * [B][513][T] uniform in [0,1) is the random initial phase; twiddles complex [512] exp(-2 pi i k/1024), window [1024]
  * periodic hann, wss [1024 + 256 (T-1)] window sum-square; workspaces: angles / reb0 / reb1 complex [B][T][513], frames
- * [B][T][1024]; wav [B][256 (T-1)].  All pointers device memory, all launches asynchronous on `stream`. */
+ * [B][T][1024]; wav [B][256 (T-1)].  All pointers device memory, all launches asynchronous on `stream`.
+ * Refused before anything is launched (non-zero return, df_last_error() names the argument, no output is touched):
+ * df_mel_to_stft -- B, n_mels or T < 1, n_mels > 128 (the size of the kernel's span tables), iters < 0 (0 returns the clipped
+ * least-squares start), a null mel / A / At / Pt / S; df_griffinlim -- B < 1, T < 2 (one frame is zero hops of audio), n_iter < 0
+ * (0 synthesises from the initial phase), momentum outside [0, 1) or NaN, any null pointer. */
 int df_mel_to_stft(const float* mel_dev, int B, int n_mels, int T, const float* A_dev, const float* At_dev,
                    const float* Pt_dev, float inv_L, int iters, float* S_dev, void* stream);
 int df_griffinlim(const float* S_dev, const float* phase0_dev, int B, int T, int n_iter, float momentum,
