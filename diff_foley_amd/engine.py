@@ -310,6 +310,12 @@ def _want_dim(what, got, want):
         raise RuntimeError(f"{what}: last dimension is {got}, the loaded model expects {want}")
 
 
+class PositionOutOfRange(IndexError, RuntimeError):
+    """More frames than the cond stage's positional table has rows.  The reference looks the positions up in an nn.Embedding
+    (video_feat_encoder.py:16), which answers an index past the table with an IndexError on the CPU and with a RuntimeError (device-side
+    assert) on a GPU: a caller that catches either catches this."""
+
+
 def _want_nchw(what, x, channels):
     """x must be [N][channels][H][W]: the engine derives every address from these four numbers."""
     if x.ndim != 4:
@@ -542,6 +548,9 @@ class Engine:
         feats = _dev_f32(feats, self.device)
         B, T, D = feats.shape
         _want_dim("get_learned_conditioning: video features", D, getattr(self, "cond_origin_dim", None))
+        seq_len = getattr(self, "cond_seq_len", None)
+        if seq_len is not None and T > int(seq_len):
+            raise PositionOutOfRange(f"get_learned_conditioning: {T} frames, the positional table has {seq_len} rows (index out of range)")
         out = torch.empty(B, T, self.cond_embed_dim, device=self.device, dtype=torch.float32)
         if out.numel() == 0:      # an empty batch / sequence gives an empty result, like the reference's Linear + pos_emb[:0]
             return out

@@ -381,6 +381,7 @@ class LatentDiffusion:
         eng.vae_embed_dim = self.vae_cfg["embed_dim"]
         eng.cond_embed_dim = self.cond_cfg["embed_dim"]
         eng.cond_origin_dim = self.cond_cfg["origin_dim"]
+        eng.cond_seq_len = self.cond_cfg["seq_len"]
         eng.unet_context_dim = self.unet_cfg["context_dim"]
         eng.unet_out_channels = self.unet_cfg["out_channels"]
         eng.unet_in_channels = self.unet_cfg["in_channels"]
@@ -507,17 +508,16 @@ class LatentDiffusion:
     def sample(self, cond, batch_size=16, return_intermediates=False, x_T=None, verbose=True, timesteps=None,
                quantize_denoised=False, mask=None, x0=None, shape=None, **kwargs):
         self._require()
-        S.reject_unsupported("LatentDiffusion.sample", dict(quantize_denoised=quantize_denoised, start_T=kwargs.get("start_T")),
-                             dict(quantize_denoised=False, start_T=None))
+        S.reject_unsupported("LatentDiffusion.sample", dict(quantize_denoised=quantize_denoised), dict(quantize_denoised=False))
         if shape is None:
             shape = (batch_size, self.channels, self.image_size, self.image_size)
         if cond is not None:
             cond = self._cond_tensor(cond)[:batch_size]
-        return S.ancestral_sample(self, cond, tuple(shape), x_T=x_T, timesteps=timesteps,
-                                  log_every_t=kwargs.get("log_every_t"), return_intermediates=return_intermediates,
-                                  noise_fn=kwargs.get("noise_fn"), callback=kwargs.get("callback"),
-                                  img_callback=kwargs.get("img_callback"), mask=mask, x0=x0,
-                                  q_noise_fn=kwargs.get("q_noise_fn"))
+        # The reference hands p_sample_loop its named parameters only (ddpm.py:1264-1268): log_every_t, callback, img_callback and
+        # start_T arriving in **kwargs have no effect there, and none here -- the intermediates follow self.log_every_t.  noise_fn and
+        # q_noise_fn are this package's replay hooks (no reference name) and are obeyed.
+        return S.ancestral_sample(self, cond, tuple(shape), x_T=x_T, timesteps=timesteps, return_intermediates=return_intermediates,
+                                  noise_fn=kwargs.get("noise_fn"), mask=mask, x0=x0, q_noise_fn=kwargs.get("q_noise_fn"))
 
     def _sampler(self, name):
         return {"DDIM": S.DDIMSampler, "DPM_Solver": S.DPMSolverSampler, "PLMS": S.PLMSSampler}[name](self)

@@ -196,12 +196,13 @@ class DDIMSampler(object):
         self.ddim_sqrt_one_minus_alphas = self.tables.sqrt_one_minus_alphas
 
     @torch.no_grad()
-    def sample(self, S, batch_size, shape, conditioning=None, eta=0.0, x_T=None, log_every_t=100,
-               unconditional_guidance_scale=1.0, unconditional_conditioning=None, temperature=1.0,
-               verbose=True, callback=None, img_callback=None, classifier=None, origin_cond=None,
-               classifier_guide_scale=0.0, mask=None, x0=None, score_corrector=None, corrector_kwargs=None,
-               noise_dropout=0.0, **kwargs):
-        reject_unsupported("DDIMSampler", kwargs)
+    def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None,
+               quantize_x0=False, eta=0.0, mask=None, x0=None, temperature=1.0, noise_dropout=0.0, score_corrector=None,
+               corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, unconditional_guidance_scale=1.0,
+               unconditional_conditioning=None, classifier=None, origin_cond=None, classifier_guide_scale=0.0, **kwargs):
+        # the reference's parameters in the reference's order (ddim.py:59-82), so that a positional call means the same; then the
+        # three of sample_with_classifier, which is this method
+        reject_unsupported("DDIMSampler", dict(kwargs, quantize_x0=quantize_x0))
         noise_fn = kwargs.get("noise_fn")       # tests: replaces the device generator (the reference run's CPU noise sequence)
         _warn_batch(conditioning, batch_size)
         self.make_schedule(S, ddim_eta=eta, verbose=verbose)
@@ -248,9 +249,16 @@ class DDIMSampler(object):
                 inter["pred_x0"].append(pred_x0)
         return img, inter
 
-    def sample_with_classifier(self, S, batch_size, shape, conditioning=None, origin_cond=None, classifier=None,
+    def sample_with_classifier(self, S, batch_size, shape, conditioning=None, origin_cond=None, callback=None, normals_sequence=None,
+                               img_callback=None, quantize_x0=False, eta=0.0, mask=None, x0=None, temperature=1.0, noise_dropout=0.0,
+                               score_corrector=None, corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100,
+                               unconditional_guidance_scale=1.0, unconditional_conditioning=None, classifier=None,
                                classifier_guide_scale=0.0, **kwargs):
-        return self.sample(S, batch_size, shape, conditioning, origin_cond=origin_cond, classifier=classifier,
+        return self.sample(S, batch_size, shape, conditioning, callback=callback, normals_sequence=normals_sequence,
+                           img_callback=img_callback, quantize_x0=quantize_x0, eta=eta, mask=mask, x0=x0, temperature=temperature,
+                           noise_dropout=noise_dropout, score_corrector=score_corrector, corrector_kwargs=corrector_kwargs,
+                           verbose=verbose, x_T=x_T, log_every_t=log_every_t, unconditional_guidance_scale=unconditional_guidance_scale,
+                           unconditional_conditioning=unconditional_conditioning, classifier=classifier, origin_cond=origin_cond,
                            classifier_guide_scale=classifier_guide_scale, **kwargs)
 
 
@@ -260,12 +268,14 @@ class PLMSSampler(object):
         self.ddpm_num_timesteps = model.num_timesteps
 
     @torch.no_grad()
-    def sample(self, S, batch_size, shape, conditioning=None, eta=0.0, x_T=None, log_every_t=100,
-               unconditional_guidance_scale=1.0, unconditional_conditioning=None, verbose=True, callback=None,
-               img_callback=None, mask=None, x0=None, score_corrector=None, corrector_kwargs=None, **kwargs):
+    def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None,
+               quantize_x0=False, eta=0.0, mask=None, x0=None, temperature=1.0, noise_dropout=0.0, score_corrector=None,
+               corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, unconditional_guidance_scale=1.0,
+               unconditional_conditioning=None, **kwargs):
+        # the reference's parameters in the reference's order (plms.py:58-81)
         if eta != 0:
             raise ValueError("ddim_eta must be 0 for PLMS")
-        reject_unsupported("PLMSSampler", kwargs, dict(temperature=1.0))
+        reject_unsupported("PLMSSampler", dict(kwargs, quantize_x0=quantize_x0, temperature=temperature), dict(temperature=1.0))
         _warn_batch(conditioning, batch_size)
         tb = DDIMTables(self.model.alphas_cumprod, S, 0.0)
         dev = self.model.device
@@ -325,11 +335,15 @@ class DPMSolverSampler(object):
         self.model = model
 
     @torch.no_grad()
-    def sample(self, S, batch_size, shape, conditioning=None, x_T=None, unconditional_guidance_scale=1.0,
-               unconditional_conditioning=None, classifier=None, origin_cond=None, classifier_guide_scale=0.0,
-               **kwargs):
-        # the reference ignores eta / temperature here (sampler.py:24-56 passes neither to DPM_Solver): same
-        reject_unsupported("DPMSolverSampler", kwargs, dict(mask=None, x0=None, score_corrector=None))   # sampler.py:24-56 accepts and drops them
+    def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None,
+               quantize_x0=False, eta=0.0, mask=None, x0=None, temperature=1.0, noise_dropout=0.0, score_corrector=None,
+               corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, unconditional_guidance_scale=1.0,
+               unconditional_conditioning=None, classifier=None, origin_cond=None, classifier_guide_scale=0.0, **kwargs):
+        # the reference's parameters in the reference's order (sampler.py:25-48), then the three of sample_with_classifier.  The
+        # reference ignores eta / temperature / noise_dropout, the callbacks and log_every_t here (sampler.py:24-56 passes none of
+        # them to DPM_Solver): same
+        reject_unsupported("DPMSolverSampler", dict(kwargs, quantize_x0=quantize_x0, mask=mask, x0=x0, score_corrector=score_corrector),
+                           dict(mask=None, x0=None, score_corrector=None))   # sampler.py:24-56 accepts and drops them
         if S < 2:
             raise AssertionError("DPM-Solver++(2M) needs steps >= order = 2 (dpm_solver.py:1083 asserts steps >= order)")
         _warn_batch(conditioning, batch_size)
@@ -382,9 +396,16 @@ class DPMSolverSampler(object):
                 m_prev[1] = model_fn(x, step)
         return x, None
 
-    def sample_with_classifier(self, S, batch_size, shape, conditioning=None, origin_cond=None, classifier=None,
+    def sample_with_classifier(self, S, batch_size, shape, conditioning=None, origin_cond=None, callback=None, normals_sequence=None,
+                               img_callback=None, quantize_x0=False, eta=0.0, mask=None, x0=None, temperature=1.0, noise_dropout=0.0,
+                               score_corrector=None, corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100,
+                               unconditional_guidance_scale=1.0, unconditional_conditioning=None, classifier=None,
                                classifier_guide_scale=0.0, **kwargs):
-        return self.sample(S, batch_size, shape, conditioning, origin_cond=origin_cond, classifier=classifier,
+        return self.sample(S, batch_size, shape, conditioning, callback=callback, normals_sequence=normals_sequence,
+                           img_callback=img_callback, quantize_x0=quantize_x0, eta=eta, mask=mask, x0=x0, temperature=temperature,
+                           noise_dropout=noise_dropout, score_corrector=score_corrector, corrector_kwargs=corrector_kwargs,
+                           verbose=verbose, x_T=x_T, log_every_t=log_every_t, unconditional_guidance_scale=unconditional_guidance_scale,
+                           unconditional_conditioning=unconditional_conditioning, classifier=classifier, origin_cond=origin_cond,
                            classifier_guide_scale=classifier_guide_scale, **kwargs)
 
 

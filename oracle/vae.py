@@ -78,5 +78,7 @@ def decode_first_stage(sd, cfg, z, scale_factor=0.18215):
 def cond_stage(sd, x):
     """Video_Feat_Encoder_Posembed.forward.  ``sd`` keys relative to ``cond_stage_model.``."""
     bs, seq_len, _ = x.shape
+    if seq_len > sd["pos_emb.weight"].shape[0]:          # nn.Embedding on arange(seq_len) (video_feat_encoder.py:16), not a broadcast add
+        raise IndexError("index out of range in self")
     y = F.linear(x, sd["embedder.0.weight"], sd["embedder.0.bias"])
     return y + sd["pos_emb.weight"][:seq_len][None]

@@ -9,6 +9,7 @@ regenerated from seeds by the tests; no reference source is copied.
 
     python tests/golden/make_golden.py --tiny     # seconds
     python tests/golden/make_golden.py --full     # ~10 min (860 M-param reference on CPU)
+    python tests/golden/make_golden.py --fuzz --signatures     # G14: every case of tests/fuzz_cases.py, ~2 min
 """
 import argparse
 import os
@@ -467,6 +468,230 @@ def quad():
     save("g11_ddim_quad.npz", **out)
 
 
+# ---------------------------------------------------------------------------------------------------------------- G14: the fuzz cases
+def _fuzz_cases():
+    sys.path.insert(0, os.path.dirname(HERE))
+    import fuzz_cases
+    return fuzz_cases
+
+
+def _fuzz_size_limit():
+    """No G14 file may be larger than the largest fixture that was there before them."""
+    return max(os.path.getsize(os.path.join(HERE, f)) for f in os.listdir(HERE) if f.endswith(".npz") and not f.startswith("g14_"))
+
+
+def _write_surface(fc, surface, records):
+    """One file per surface; a surface whose file would pass the size limit is split by seed ranges into _p1, _p2, ..."""
+    assert sorted(records) == fc.suite_seeds(surface)
+    limit = _fuzz_size_limit()
+    for old in fc.record_files(surface):
+        os.remove(old)
+    seeds = sorted(records)
+    for parts in range(1, len(seeds) + 1):
+        chunks = [seeds[len(seeds) * i // parts:len(seeds) * (i + 1) // parts] for i in range(parts)]
+        names = [f"g14_fuzz_{surface}.npz" if parts == 1 else f"g14_fuzz_{surface}_p{i + 1}.npz" for i in range(parts)]
+        for name, chunk in zip(names, chunks):
+            np.savez_compressed(os.path.join(HERE, name), **fc.flatten_records({s: records[s] for s in chunk}))
+        sizes = [os.path.getsize(os.path.join(HERE, n)) for n in names]
+        if max(sizes) <= limit:
+            for n, s in zip(names, sizes):
+                print(f"wrote {n}: {s / 1024:.1f} KiB")
+            return
+        for n in names:
+            os.remove(os.path.join(HERE, n))
+    raise RuntimeError(f"{surface}: one record alone is larger than {limit} bytes")
+
+
+class _ReplayQNoise:
+    """q_sample's torch.randn_like(x0) (ddpm.py:279-282) fed from its own seeded generator, as in inpaint() above."""
+
+    def __init__(self):
+        self.g = torch.Generator()
+
+    def __enter__(self):
+        self.real = torch.randn_like
+        torch.randn_like = lambda t, **kw: torch.randn(t.shape, generator=self.g)
+        return self.g
+
+    def __exit__(self, *a):
+        torch.randn_like = self.real
+
+
+def fuzz(only=None):
+    """G14: the REFERENCE on every case the randomised GPU tests draw (tests/fuzz_cases.py): range(N_CASES) of each surface and its
+    regression seeds, whatever DF_FUZZ_* says.  Same synth weights and seeded inputs as the tests; the record format is fuzz_cases'."""
+    fc = _fuzz_cases()
+    t0 = time.time()
+    want = lambda s: only is None or s in only
+
+    def note(surface, seed):
+        print(f"  {surface} {seed}: {time.time() - t0:.0f}s", flush=True)
+
+    if want("unet"):
+        recs = {}
+        for seed in fc.suite_seeds("unet"):
+            k = fc.unet_case(seed)
+            model, _ = ref_import.build_reference_ldm(ref_import.load_ldm_config(unet=k["cfg"], vae=synth.VAE_TINY, cond=k["cond"]), k["sd"])
+            B = k["o"]["B"]
+            with torch.no_grad():
+                y = model.apply_model(k["x"], k["t"], k["c"])
+                e2 = model.apply_model(torch.cat([k["x"], k["x"]]), torch.cat([k["tt"], k["tt"]]), torch.cat([k["uc"], k["c"]]))
+            recs[seed] = dict(draw=fc.draw_json("unet", seed), y=fc.pack_value(y, seed),
+                              y_cfg=fc.pack_value(e2[:B] + fc.UNET_CFG_SCALE * (e2[B:] - e2[:B]), seed))
+            note("unet", seed)
+        _write_surface(fc, "unet", recs)
+    if want("vae"):
+        recs = {}
+        for seed in fc.suite_seeds("vae"):
+            k = fc.vae_case(seed)
+            model, _ = ref_import.build_reference_ldm(ref_import.load_ldm_config(unet=synth.UNET_TINY, vae=k["cfg"], cond=synth.COND_TINY), k["sd"])
+            with torch.no_grad():
+                recs[seed] = dict(draw=fc.draw_json("vae", seed), y=fc.pack_value(model.decode_first_stage(k["z"]), seed))
+            note("vae", seed)
+        _write_surface(fc, "vae", recs)
+    if want("cond"):
+        recs = {}
+        for seed in fc.suite_seeds("cond"):
+            k = fc.cond_case(seed)
+            model, _ = ref_import.build_reference_ldm(ref_import.load_ldm_config(unet=k["ucfg"], vae=synth.VAE_TINY, cond=k["cond"]), k["sd"])
+            rec = dict(draw=fc.draw_json("cond", seed))
+            with torch.no_grad():
+                for i, f in enumerate(k["feats"]):
+                    rec[f"c{i}"] = fc.pack_value(model.get_learned_conditioning(f), seed)
+                try:                                    # longer than the positional table
+                    model.get_learned_conditioning(torch.zeros(1, k["cond"]["seq_len"] + 1, k["cond"]["origin_dim"]))
+                except Exception as ex:
+                    rec["too_long_raises"] = type(ex).__name__
+            recs[seed] = rec
+            note("cond", seed)
+        _write_surface(fc, "cond", recs)
+    if want("classifier"):
+        recs = {}
+        for seed in fc.suite_seeds("classifier"):
+            k = fc.classifier_case(seed)
+            cls = ref_import.build_reference_classifier(dict(k["cfg"]), k["sd"])
+            xin = k["x"].clone().requires_grad_(True)
+            p = cls(xin, context=k["vf"], timesteps=k["t"])
+            g = torch.autograd.grad(torch.log(p).sum(), xin)[0]
+            recs[seed] = dict(draw=fc.draw_json("classifier", seed), p=fc.pack_value(p, seed), grad=fc.pack_value(g, seed))
+            note("classifier", seed)
+        _write_surface(fc, "classifier", recs)
+    if want("cavp"):
+        CAVP_Inference = ref_import.import_reference_cavp()
+        import model.cavp_modules as cm
+        recs = {}
+        for seed in fc.suite_seeds("cavp"):
+            k = fc.cavp_case(seed)
+            m = CAVP_Inference("Slowonly_pool", "cnn14_pool", k["cfg"]["embed_dim"])
+            m.video_encoder = cm.ResNet3dSlowOnly(depth=50, pretrained=None, stage_blocks=tuple(k["cfg"]["stage_blocks"]))
+            m.eval()
+            missing, unexpected = m.load_state_dict(k["sd"], strict=False)
+            assert not unexpected and all(not x.startswith("video_") or "num_batches" in x for x in missing), (missing, unexpected)
+            with torch.no_grad():
+                recs[seed] = dict(draw=fc.draw_json("cavp", seed),
+                                  feats=fc.pack_value(m.encode_video(k["video"], normalize=True, pool=False), seed),
+                                  feats_raw=fc.pack_value(m.encode_video(k["video"], normalize=False, pool=False), seed))
+            note("cavp", seed)
+        _write_surface(fc, "cavp", recs)
+    if want("samplers") or want("double_guidance"):
+        sd = synth.make_state_dict(synth.state_dict_spec(synth.UNET_TINY, synth.VAE_TINY, synth.COND_TINY), 0)
+        model, _ = ref_import.build_reference_ldm(ref_import.load_ldm_config(unet=synth.UNET_TINY, vae=synth.VAE_TINY, cond=synth.COND_TINY), sd)
+        default_log_every_t = model.log_every_t
+    if want("samplers"):
+        recs = {}
+        for seed in fc.suite_seeds("samplers"):
+            k = fc.sampler_case(seed)
+            o = k["o"]
+            B, W, S, name = o["B"], o["W"], o["S"], o["name"]
+            rec = dict(draw=fc.draw_json("samplers", seed))
+            kw = dict(x_T=k["xT"].clone())
+            if o["inpaint"]:
+                kw.update(mask=k["mask"], x0=k["x0"])
+            with torch.no_grad(), _ReplayQNoise() as gq:
+                c = model.get_learned_conditioning(k["feats"])
+
+                def seed_all():
+                    gq.manual_seed(k["q_seed"])
+                    torch.manual_seed(k["noise_seed"])
+                try:
+                    seed_all()
+                    if name == "DDPM":          # sample() hands none of its **kwargs to p_sample_loop (ddpm.py:1253-1268): the option is the
+                        model.log_every_t = o["log_every_t"]          # model's attribute
+                        z, inter = model.sample(c, batch_size=B, return_intermediates=True, timesteps=S, shape=(B, 4, 16, W), verbose=False, **kw)
+                        rec["n_inter"] = len(inter)
+                        seed_all()              # ... and a log_every_t argument changes nothing
+                        z1, inter1 = model.sample(c, batch_size=B, return_intermediates=True, timesteps=S, shape=(B, 4, 16, W), verbose=False,
+                                                  log_every_t=1, **kw)
+                        rec["n_inter_kwarg_1"] = len(inter1)
+                        rec["kwarg_latents_equal"] = bool(torch.equal(z, z1))
+                    else:
+                        if name == "DDIM":
+                            kw.update(eta=o["eta"], temperature=o["temperature"], noise_dropout=o["noise_dropout"])
+                        if name != "DPM_Solver":
+                            kw.update(log_every_t=o["log_every_t"])
+                        z, inter = model.sample_log_diff_sampler(c, B, name, S, size_len=W, unconditional_guidance_scale=o["scale"],
+                                                                 unconditional_conditioning=k["uc"], **kw)
+                        if inter is not None:
+                            rec["n_x_inter"], rec["n_pred_x0"] = len(inter["x_inter"]), len(inter["pred_x0"])
+                            rec["pred_x0_last"] = fc.pack_value(inter["pred_x0"][-1], seed)
+                    rec["z"] = fc.pack_value(z, seed)
+                except (IndexError, AssertionError, ValueError) as ex:
+                    rec["raises"] = type(ex).__name__
+                finally:
+                    model.log_every_t = default_log_every_t
+            recs[seed] = rec
+            note("samplers", seed)
+        _write_surface(fc, "samplers", recs)
+    if want("double_guidance"):
+        cls = ref_import.build_reference_classifier(dict(synth.CLS_TINY), synth.make_state_dict(synth.classifier_spec(synth.CLS_TINY), 0))
+
+        class Wrap:
+            def __call__(self, x, t, video_feat):
+                return cls(x, context=video_feat, timesteps=t)
+        recs = {}
+        for seed in fc.suite_seeds("double_guidance"):
+            k = fc.double_guidance_case(seed)
+            o = k["o"]
+            with torch.no_grad():
+                c = model.get_learned_conditioning(k["vf"][:, :32])
+                torch.manual_seed(k["noise_seed"])
+                z, _ = model.sample_log_with_classifier_diff_sampler(
+                    c, origin_cond=k["vf"], batch_size=o["B"], sampler_name=o["name"], ddim_steps=o["S"], size_len=o["W"],
+                    unconditional_guidance_scale=o["scale"], unconditional_conditioning=torch.zeros_like(c), classifier=Wrap(),
+                    classifier_guide_scale=o["cscale"], x_T=k["xT"].clone(), **(dict(eta=o["eta"]) if o["name"] == "DDIM" else {}))
+            recs[seed] = dict(draw=fc.draw_json("double_guidance", seed), z=fc.pack_value(z, seed))
+            note("double_guidance", seed)
+        _write_surface(fc, "double_guidance", recs)
+
+
+def signatures():
+    """G14: parameter names, order and repr of the defaults of the reference entry points the facade stands in for."""
+    import inspect
+    import json
+    ns = ref_import.import_reference()
+    CAVP_Inference = ref_import.import_reference_cavp()
+    LD = ns.LatentDiffusion
+    points = {"LatentDiffusion.sample": LD.sample, "LatentDiffusion.sample_log": LD.sample_log,
+              "LatentDiffusion.sample_log_diff_sampler": LD.sample_log_diff_sampler,
+              "LatentDiffusion.sample_log_with_classifier": LD.sample_log_with_classifier,
+              "LatentDiffusion.sample_log_with_classifier_diff_sampler": LD.sample_log_with_classifier_diff_sampler,
+              "LatentDiffusion.apply_model": LD.apply_model, "LatentDiffusion.decode_first_stage": LD.decode_first_stage,
+              "LatentDiffusion.get_learned_conditioning": LD.get_learned_conditioning,
+              "DDIMSampler.sample": ns.DDIMSampler.sample, "DDIMSampler.sample_with_classifier": ns.DDIMSampler.sample_with_classifier,
+              "PLMSSampler.sample": ns.PLMSSampler.sample, "DPMSolverSampler.sample": ns.DPMSolverSampler.sample,
+              "DPMSolverSampler.sample_with_classifier": ns.DPMSolverSampler.sample_with_classifier,
+              "CAVP_Inference.encode_video": CAVP_Inference.encode_video}
+    out = {}
+    for name, fn in points.items():
+        out[name] = [dict(name=p.name, kind=p.kind.name, default=None if p.default is inspect.Parameter.empty else repr(p.default))
+                     for p in inspect.signature(fn).parameters.values()]
+    path = os.path.join(HERE, "g14_signatures.json")
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print(f"wrote g14_signatures.json: {os.path.getsize(path) / 1024:.1f} KiB")
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--tiny", action="store_true")
@@ -478,8 +703,15 @@ if __name__ == "__main__":
     ap.add_argument("--quad", action="store_true", help="G11: the 'quad' DDIM discretisation tables (seconds)")
     ap.add_argument("--stochastic", action="store_true", help="G12: eta > 0 DDIM with temperature / noise_dropout (tiny, seconds)")
     ap.add_argument("--full-extra", action="store_true", help="G5 extension: DDIM-25 reference runs for seeds 23 / 24 (~4 min)")
+    ap.add_argument("--fuzz", nargs="*", metavar="SURFACE", help="G14: the reference on every case of tests/fuzz_cases.py (all surfaces, "
+                    "or the ones named); a few minutes")
+    ap.add_argument("--signatures", action="store_true", help="G14: signatures of the reference entry points the facade stands in for")
     a = ap.parse_args()
     torch.set_num_threads(8)
+    if a.fuzz is not None:
+        fuzz(set(a.fuzz) or None)
+    if a.signatures:
+        signatures()
     if a.tiny:
         tiny()
     if a.full:

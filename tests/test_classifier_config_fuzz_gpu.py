@@ -8,15 +8,16 @@ G6 pins the tiny and the full configuration; the tape builder has a branch per b
 Tolerance (fp16-operand build): probability within 5e-3, gradient rel-L2 < 1.5e-2 (the full-size configuration measures 3.7e-3)."""
 import os
 
-import numpy as np
 import pytest
 import torch
 
-from helpers import fuzz_seeds, rel_l2, tiny_state_dict
+import fuzz_cases
+from helpers import fuzz_record_for_run, fuzz_seeds, record_rel_l2, rel_l2, tiny_state_dict
 
 pytestmark = pytest.mark.gpu
 
-N_CASES = 10
+N_CASES = fuzz_cases.N_CASES["classifier"]
+REGRESSION_SEEDS = fuzz_cases.REGRESSION_SEEDS["classifier"]
 
 
 PREC = os.environ.get("DF_FUZZ_PREC", "fp16")          # exploratory: the bf16-operand build (8 x the rounding unit), in-plan autotuner
@@ -25,57 +26,23 @@ TUNE = os.environ.get("DF_FUZZ_TUNE", "0") != "0"
 WIDE = os.environ.get("DF_FUZZ_WIDE", "0") != "0"      # exploratory sweeps: wider maps, batches and widths than the suite draws
 
 
-def _draw(seed):
-    r = np.random.default_rng(5200 + seed)
-    while True:
-        mc = int(r.choice([64, 128, 192, 320] if WIDE else [64, 128]))
-        mult = [list(m) for m in ([1, 2], [1, 2, 2], [1, 1, 2], [1, 2, 4], [1, 1])][int(r.integers(0, 5))]
-        nrb = int(r.choice([1, 2]))
-        levels = len(mult)
-        att = sorted(int(2 ** i) for i in range(levels) if r.random() < 0.6)
-        chs = {mc * mult[i] for i in range(levels) if 2 ** i in att} | {mc * mult[-1]}
-        heads = [h for h in (1, 2, 4, 8, 16) if all(ch % h == 0 and ch // h in (32, 64) for ch in chs)]      # the backward's head dims
-        if heads:
-            break
-    cfg = dict(in_channels=4, out_channels=1, model_channels=mc, attention_resolutions=att, num_res_blocks=nrb, channel_mult=mult,
-               num_heads=int(r.choice(heads)), context_dim=int(r.choice([64, 128, 512])))
-    q = 2 ** (levels - 1)
-    if WIDE:
-        H = int(r.choice([h for h in (8, 16, 24, 32) if h % q == 0]))
-        W = int(r.choice([w for w in (8, 16, 24, 32, 40, 64, 96) if w % q == 0]))
-        return cfg, dict(B=int(r.choice([1, 2, 3, 4, 5, 8])), H=H, W=W, T=int(r.choice([1, 8, 31, 32, 33, 40])))
-    H = int(r.choice([h for h in (8, 16) if h % q == 0]))
-    W = int(r.choice([w for w in (16, 32, 64) if w % q == 0]))
-    return cfg, dict(B=int(r.choice([1, 2, 3])), H=H, W=W, T=int(r.choice([8, 32, 33])))
-
-
-# seeds a wider sweep (DF_FUZZ_SEED0=100 DF_FUZZ_CASES=60, round 6) failed on: model_channels 64 with channel_mult [1, 1] -- the head's
-# conv halves 64 channels to 32, and the backward-data packing refused a Cout that is not a multiple of the 64-channel K step
-REGRESSION_SEEDS = [119, 152]
-
-
 @pytest.mark.parametrize("seed", sorted(set(fuzz_seeds(N_CASES)) | set(REGRESSION_SEEDS)))
 def test_classifier_gradient_product_vs_autograd(seed):
     import diff_foley_amd as P
     from diff_foley_amd import synth
     from oracle import unet as ou, samplers as osamp
-    cfg, o = _draw(seed)
+    k = fuzz_cases.classifier_case(seed, WIDE)
+    cfg, o, sd = k["cfg"], k["o"], k["sd"]
     host = P.LatentDiffusion(precision=PREC, **P.stage2_config(synth.UNET_TINY, synth.VAE_TINY, synth.COND_TINY))
     host.load_state_dict(tiny_state_dict())
     host.cuda()
     if TUNE:
         host.autotune(True)
-    sd = synth.make_state_dict(synth.classifier_spec(cfg), 500 + seed)
     cls = P.AlignmentClassifier(classifier_config=dict(params=dict(cfg)))
     cls.load_state_dict(sd)
     cls.attach(host)
     csd = ou.sub_state_dict(sd, "model.")
-    g = torch.Generator().manual_seed(600 + seed)
-    B, H, W, T = o["B"], o["H"], o["W"], o["T"]
-    x = torch.randn(B, 4, H, W, generator=g)
-    vf = torch.randn(B, T, cfg["context_dim"], generator=g)
-    vf = vf / vf.norm(dim=-1, keepdim=True)
-    t = torch.randint(0, 1000, (B,), generator=g).float()
+    x, vf, t = k["x"], k["vf"], k["t"]
     p_ref = ou.classifier_forward(csd, cfg, x, t, vf).detach()
     g_ref = osamp.classifier_grad(lambda xx, tt, cc: ou.classifier_forward(csd, cfg, xx, tt, cc), x, t, vf)
     p = cls(x.cuda(), t=t.cuda(), video_feat=vf.cuda()).cpu()
@@ -88,6 +55,15 @@ def test_classifier_gradient_product_vs_autograd(seed):
     assert torch.allclose(p, p_ref, atol=5e-3 * PREC_SCALE) and torch.allclose(prob.cpu(), p_ref, atol=5e-3 * PREC_SCALE), (cfg, o)
     assert err < 1.5e-2 * PREC_SCALE, (cfg, o, err)
     assert max(per) < 1.5e-2 * PREC_SCALE, (cfg, o, per)
+    # ... and against the reference's own probability and gradient on this case, by the same metrics and bounds
+    rec = fuzz_record_for_run("classifier", seed, dict(cfg=cfg, o=o), WIDE)
+    if rec is not None:
+        p_rec, g_rec = torch.from_numpy(rec["p"]["full"]), torch.from_numpy(rec["grad"]["full"])
+        err_r, per_r = record_rel_l2(rec["grad"], grad), _per_sample(grad.cpu(), g_rec)
+        print(f"case {seed}: against the reference's record -> grad rel-L2 {err_r:.2e}, per sample {[f'{e:.1e}' for e in per_r]}")
+        assert torch.allclose(p, p_rec, atol=5e-3 * PREC_SCALE) and torch.allclose(prob.cpu(), p_rec, atol=5e-3 * PREC_SCALE), (cfg, o)
+        assert err_r < 1.5e-2 * PREC_SCALE, (cfg, o, err_r)
+        assert max(per_r) < 1.5e-2 * PREC_SCALE, (cfg, o, per_r)
 
 
 @pytest.mark.parametrize("name,S", [("DDIM", 4), ("DPM_Solver", 4)])

@@ -9,16 +9,16 @@ Tolerance: rel-L2 of the final latent < 1e-2 on the fp16-operand build of the ti
 cases; a wrong coefficient, table index, noise order or blend is an O(0.1 .. 1) difference)."""
 import os
 
-import numpy as np
 import pytest
 import torch
 
-from helpers import fuzz_seeds, rel_l2, tiny_state_dict
+import fuzz_cases
+from helpers import fuzz_record_for_run, fuzz_seeds, record_rel_l2, rel_l2, tiny_state_dict
 
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-2
-N_CASES = 16
+N_CASES = fuzz_cases.N_CASES["samplers"]
 WIDE = os.environ.get("DF_FUZZ_WIDE", "0") != "0"
 
 
@@ -45,64 +45,39 @@ def oracle_tiny():
     return apply_model, cond, sched
 
 
-def _draw(seed):
-    """One option set.  Everything the case needs is a function of the seed."""
-    r = np.random.default_rng(7000 + seed)
-    name = ["DDIM", "PLMS", "DPM_Solver", "DDPM"][seed % 4]            # every sampler gets its share whatever N_CASES is
-    o = dict(name=name, B=int(r.choice([1, 2, 3])), W=int(r.choice([32, 64])), T=int(r.choice([1, 17, 32, 40])))
-    if WIDE:      # exploratory sweeps (DF_FUZZ_WIDE=1): more batches, latent widths (multiples of the UNet's 8 x downsampling) and contexts
-        o = dict(name=name, B=int(r.choice([1, 2, 3, 4, 5, 7])), W=int(r.choice([8, 16, 24, 32, 40, 64, 72, 96])),
-                 T=int(r.choice([1, 2, 17, 31, 32, 33, 40])))
-    o["S"] = int(r.integers(4, 11)) if name != "DPM_Solver" else int(r.choice([2, 3, 7, 12, 16]))
-    if name == "DDPM":
-        o["S"] = int(r.integers(3, 7))
-    if o["S"] == 9 and seed != 0:         # S = 9 is the reference's IndexError case (below): once is enough
-        o["S"] = 8
-    o["scale"] = float(r.choice([1.0, 2.5, 4.5, 7.0]))
-    o["uc"] = str(r.choice(["zeros", "random", "none"]))
-    o["eta"] = float(r.choice([0.0, 0.0, 0.5, 1.0])) if name == "DDIM" else 0.0
-    o["temperature"] = float(r.choice([1.0, 0.7, 1.3])) if o["eta"] else 1.0
-    o["noise_dropout"] = float(r.choice([0.0, 0.3])) if o["eta"] else 0.0
-    o["log_every_t"] = int(r.choice([1, 3, 100]))
-    o["inpaint"] = bool(r.random() < 0.35) and name != "DPM_Solver"      # the DPM-Solver sampler's reference drops mask / x0
-    o["seed"] = seed
-    return o
-
-
 @pytest.mark.parametrize("seed", fuzz_seeds(N_CASES))
 def test_sampler_options_product_vs_oracle(tiny16, oracle_tiny, seed):
     from oracle import samplers as osamp
     apply_model, cond_fn, sched = oracle_tiny
     acp = sched["alphas_cumprod"]
-    o = _draw(seed)
+    k = fuzz_cases.sampler_case(seed, WIDE)
+    o = k["o"]
+    rec = fuzz_record_for_run("samplers", seed, o, WIDE)          # the reference's own run of this case
     B, W, S, name = o["B"], o["W"], o["S"], o["name"]
-    g = torch.Generator().manual_seed(9000 + seed)
-    feats = torch.randn(B, o["T"], 64, generator=g)
-    feats = feats / feats.norm(dim=-1, keepdim=True)
-    xT = torch.randn(B, 4, 16, W, generator=g)
+    feats, xT, uc_ref, x0, mask = k["feats"], k["xT"], k["uc"], k["x0"], k["mask"]
     c_ref = cond_fn(feats)
     c = tiny16.get_learned_conditioning(feats.cuda())
     assert rel_l2(c.cpu(), c_ref) < 5e-3
-    uc_ref = {"zeros": torch.zeros_like(c_ref), "random": 0.5 * torch.randn(c_ref.shape, generator=g), "none": None}[o["uc"]]
     uc = None if uc_ref is None else uc_ref.cuda()
-    x0 = torch.randn(B, 4, 16, W, generator=g) if o["inpaint"] else None
-    mask = (torch.rand(B, 1, 16, W, generator=g) < 0.5).float() if o["inpaint"] else None
     gq = torch.Generator()
     qn = lambda shape: torch.randn(tuple(shape), generator=gq)
     noise = lambda s: torch.randn(tuple(s))                  # the global CPU generator, like the reference (and F.dropout's mask)
 
     def seed_all():
-        gq.manual_seed(100 + seed)
-        torch.manual_seed(200 + seed)
+        gq.manual_seed(k["q_seed"])
+        torch.manual_seed(k["noise_seed"])
 
     # ---- a step count whose uniform grid runs past the schedule (S = 9: 999 + 1; util.py:48-57) fails in the reference with an
     # IndexError when the tables are gathered; the product fails the same way, before any launch
-    if name in ("DDIM", "PLMS") and (np.arange(0, 1000, 1000 // S) + 1).max() >= 1000:
+    if fuzz_cases.sampler_grid_overruns(o):
         with pytest.raises(IndexError):
             osamp.ddim_sample(apply_model, acp, S, xT, c_ref) if name == "DDIM" else osamp.plms_sample(apply_model, acp, S, xT, c_ref)
-        with pytest.raises(IndexError):
+        with pytest.raises(IndexError) as ei:
             tiny16.sample_log_diff_sampler(c, B, name, S, size_len=W, x_T=xT.clone())
+        if rec is not None:
+            assert rec.get("raises") == type(ei.value).__name__, (rec.get("raises"), ei.value)
         return
+    assert rec is None or "raises" not in rec, rec.get("raises")
     # ---- oracle
     seed_all()
     if name == "DDIM":
@@ -123,9 +98,17 @@ def test_sampler_options_product_vs_oracle(tiny16, oracle_tiny, seed):
     if o["inpaint"]:
         kw.update(mask=mask, x0=x0, q_noise_fn=qn)
     if name == "DDPM":
-        z, inter = tiny16.sample(c, batch_size=B, return_intermediates=True, timesteps=S, shape=(B, 4, 16, W), noise_fn=noise,
-                                 log_every_t=o["log_every_t"], **kw)
+        # sample() hands p_sample_loop none of its **kwargs (ddpm.py:1253-1268), so the option is the model's log_every_t attribute
+        # (the oracle restates p_sample_loop, which takes it as a parameter)
+        keep = tiny16.log_every_t
+        tiny16.log_every_t = o["log_every_t"]
+        try:
+            z, inter = tiny16.sample(c, batch_size=B, return_intermediates=True, timesteps=S, shape=(B, 4, 16, W), noise_fn=noise, **kw)
+        finally:
+            tiny16.log_every_t = keep
         assert len(inter) == len(inter_ref), o
+        if rec is not None:
+            assert len(inter) == rec["n_inter"], (o, len(inter), rec["n_inter"])
     else:
         if name == "DDIM":
             kw.update(eta=o["eta"], temperature=o["temperature"], noise_dropout=o["noise_dropout"], noise_fn=noise)
@@ -135,16 +118,53 @@ def test_sampler_options_product_vs_oracle(tiny16, oracle_tiny, seed):
                                                   unconditional_conditioning=uc, **kw)
         if name == "DPM_Solver":
             assert inter is None
+            assert rec is None or not any(f.startswith("n_") for f in rec), rec.keys()
         else:
             assert len(inter["x_inter"]) == len(inter_ref["x_inter"]) and len(inter["pred_x0"]) == len(inter_ref["pred_x0"]), o
             assert rel_l2(inter["pred_x0"][-1].cpu(), inter_ref["pred_x0"][-1]) < TOL, o
+            if rec is not None:
+                assert (len(inter["x_inter"]), len(inter["pred_x0"])) == (rec["n_x_inter"], rec["n_pred_x0"]), o
+                assert record_rel_l2(rec["pred_x0_last"], inter["pred_x0"][-1]) < TOL, o
     assert z.shape == z_ref.shape and z.dtype == torch.float32 and torch.isfinite(z).all(), o
     err = rel_l2(z.cpu(), z_ref)
     print(f"case {seed}: {o} -> rel-L2 {err:.2e}")
     assert err < TOL, (o, err)
+    if rec is not None:
+        err_r = record_rel_l2(rec["z"], z)
+        print(f"case {seed}: against the reference's record -> rel-L2 {err_r:.2e}")
+        assert err_r < TOL, (o, err_r)
 
 
-@pytest.mark.parametrize("seed", fuzz_seeds(6))
+def test_sample_ignores_a_log_every_t_argument_like_the_reference(tiny16):
+    """LatentDiffusion.sample() of the reference forwards none of its **kwargs to p_sample_loop (ddpm.py:1253-1268): log_every_t (and
+    callback / img_callback) given to sample() change nothing, the intermediates follow model.log_every_t.  The reference's own pair
+    of runs is on record (n_inter_kwarg_1 == n_inter, equal latents); here sample(log_every_t=1) returns what sample() returns."""
+    seed = next(s for s in fuzz_cases.suite_seeds("samplers") if fuzz_cases.sampler_draw(s)["name"] == "DDPM"
+                and fuzz_cases.sampler_draw(s)["log_every_t"] != 1)
+    k = fuzz_cases.sampler_case(seed)
+    o = k["o"]
+    rec = fuzz_record_for_run("samplers", seed, o)
+    assert rec is not None and rec["n_inter_kwarg_1"] == rec["n_inter"] and rec["kwarg_latents_equal"] is True
+    B, W, S = o["B"], o["W"], o["S"]
+    c = tiny16.get_learned_conditioning(k["feats"].cuda())
+    gq = torch.Generator()
+    kw = dict(x_T=k["xT"].clone(), noise_fn=lambda s: torch.randn(tuple(s)))
+    if o["inpaint"]:
+        kw.update(mask=k["mask"], x0=k["x0"], q_noise_fn=lambda shape: torch.randn(tuple(shape), generator=gq))
+    calls = []
+    out = []
+    for extra in (dict(), dict(log_every_t=1, callback=calls.append, img_callback=lambda img, i: calls.append(i))):
+        gq.manual_seed(k["q_seed"])
+        torch.manual_seed(k["noise_seed"])
+        out.append(tiny16.sample(c, batch_size=B, return_intermediates=True, timesteps=S, shape=(B, 4, 16, W), **kw, **extra))
+    (z0, inter0), (z1, inter1) = out
+    assert torch.equal(z0, z1) and len(inter0) == len(inter1) and not calls
+    # the count is model.log_every_t's: x_T, the first step's image (i == S - 1) and those of the steps it divides
+    assert len(inter0) == 1 + len([i for i in range(S) if i % tiny16.log_every_t == 0 or i == S - 1])
+    assert record_rel_l2(rec["z"], z0) < TOL
+
+
+@pytest.mark.parametrize("seed", fuzz_seeds(fuzz_cases.N_CASES["double_guidance"]))
 def test_double_guidance_options_product_vs_oracle(tiny16, oracle_tiny, seed):
     """The classifier-guided samplers (ddim.py:276-396, dpm_solver/sampler.py:90-156 -> dpm_solver.py:1377-1393) over their options:
     sampler, steps, batch, latent width, CFG scale, classifier scale (0 = the gradient is formed and multiplied away), video frames
@@ -154,35 +174,26 @@ def test_double_guidance_options_product_vs_oracle(tiny16, oracle_tiny, seed):
     from helpers import tiny_classifier_sd
     from oracle import unet as ou, samplers as osamp
     apply_model, cond_fn, sched = oracle_tiny
-    r = np.random.default_rng(7600 + seed)
-    name = ["DDIM", "DPM_Solver"][seed % 2]
-    B, W = int(r.choice([1, 2, 3])), int(r.choice([32, 64]))
-    S = int(r.choice([4, 6, 8])) if name == "DDIM" else int(r.choice([3, 6, 16]))
-    scale, cscale = float(r.choice([2.5, 4.5])), float(r.choice([0.0, 10.0, 50.0]))
-    F = int(r.choice([8, 32, 33]))
-    if WIDE:
-        B, W, F = int(r.choice([1, 2, 3, 4, 5])), int(r.choice([8, 16, 24, 32, 40, 64, 96])), int(r.choice([1, 8, 31, 32, 33, 40]))
-    eta = float(r.choice([0.0, 1.0])) if name == "DDIM" else 0.0
+    k = fuzz_cases.double_guidance_case(seed, WIDE)
+    o = k["o"]
+    name, B, W, S, scale, cscale, F, eta = (o[f] for f in ("name", "B", "W", "S", "scale", "cscale", "F", "eta"))
     cls = P.AlignmentClassifier(classifier_config=dict(params=dict(synth.CLS_TINY)))
     cls.load_state_dict(tiny_classifier_sd())
     cls.attach(tiny16)
     ksd = ou.sub_state_dict(tiny_classifier_sd(), "model.")
     classifier = lambda x, t, c: ou.classifier_forward(ksd, synth.CLS_TINY, x, t, c)
-    g = torch.Generator().manual_seed(9600 + seed)
-    vf = torch.randn(B, F, 64, generator=g)
-    vf = vf / vf.norm(dim=-1, keepdim=True)
-    xT = torch.randn(B, 4, 16, W, generator=g)
+    vf, xT = k["vf"], k["xT"]
     c_ref = cond_fn(vf[:, :32])
     c = tiny16.get_learned_conditioning(vf[:, :32].cuda())
     noise = lambda s: torch.randn(tuple(s))
-    torch.manual_seed(300 + seed)
+    torch.manual_seed(k["noise_seed"])
     if name == "DDIM":
         z_ref, _ = osamp.ddim_sample(apply_model, sched["alphas_cumprod"], S, xT, c_ref, scale, torch.zeros_like(c_ref), eta=eta,
                                      classifier=classifier, origin_cond=vf, classifier_scale=cscale, noise_fn=noise)
     else:
         z_ref, _ = osamp.dpm_solver_sample(apply_model, sched["alphas_cumprod"], S, xT, c_ref, scale, torch.zeros_like(c_ref),
                                            classifier=classifier, origin_cond=vf, classifier_scale=cscale)
-    torch.manual_seed(300 + seed)
+    torch.manual_seed(k["noise_seed"])
     kw = dict(eta=eta, noise_fn=noise) if name == "DDIM" else {}
     z, _ = tiny16.sample_log_with_classifier_diff_sampler(
         c, origin_cond=vf.cuda(), batch_size=B, sampler_name=name, ddim_steps=S, size_len=W, unconditional_guidance_scale=scale,
@@ -190,3 +201,8 @@ def test_double_guidance_options_product_vs_oracle(tiny16, oracle_tiny, seed):
     err = rel_l2(z.cpu(), z_ref)
     print(f"double guidance case {seed}: {name}-{S} B={B} W={W} scale={scale} classifier scale={cscale} frames={F} eta={eta} -> rel-L2 {err:.2e}")
     assert z.shape == z_ref.shape and err < TOL, (name, S, B, W, scale, cscale, F, eta, err)
+    rec = fuzz_record_for_run("double_guidance", seed, o, WIDE)          # ... and against the reference's own run of this case
+    if rec is not None:
+        err_r = record_rel_l2(rec["z"], z)
+        print(f"double guidance case {seed}: against the reference's record -> rel-L2 {err_r:.2e}")
+        assert err_r < TOL, (o, err_r)

@@ -11,52 +11,22 @@ a single level pair, head dimensions 32 .. 160).
 Tolerance: rel-L2 < 5e-3 for one forward on the fp16-operand build (the tiny configuration's forward sits at 1e-3 .. 1.5e-3)."""
 import os
 
-import numpy as np
 import pytest
 import torch
 
-from helpers import fuzz_seeds, rel_l2
+import fuzz_cases
+from helpers import fuzz_record_for_run, fuzz_seeds, record_rel_l2, rel_l2
 
 pytestmark = pytest.mark.gpu
 
 TOL = 5e-3
-N_CASES = 12
+N_CASES = fuzz_cases.N_CASES["unet"]
 
 
 PREC = os.environ.get("DF_FUZZ_PREC", "fp16")          # exploratory: the bf16-operand build (8 x the rounding unit)
 PREC_SCALE = 8.0 if PREC == "bf16" else 1.0
 TUNE = os.environ.get("DF_FUZZ_TUNE", "0") != "0"
 WIDE = os.environ.get("DF_FUZZ_WIDE", "0") != "0"      # exploratory sweeps: wider maps, batches, contexts and widths than the suite draws
-# csrc/attention.hip:attention_supported; the suite's draws keep the head dims of the Stage-2 model and the classifier
-HEAD_DIMS = (16, 24, 32, 40, 48, 56, 64, 72, 80, 96, 112, 128, 160, 192) if WIDE else (32, 40, 64, 80, 128, 160)
-
-
-def _draw(seed):
-    r = np.random.default_rng(4200 + seed)
-    while True:         # channel_mult[0] = 1: the reference's `out` conv takes model_channels inputs (openai_unetmodel.py:682-686)
-        mc = int(r.choice([64, 128, 192, 256, 320] if WIDE else [64, 128, 192]))
-        mult = [list(m) for m in ([1, 2], [1, 2, 4], [1, 1, 2], [1, 2, 2, 4], [1, 3], [1, 1], [1, 2, 4, 4])][int(r.integers(0, 7))]
-        nrb = int(r.choice([1, 2, 3]))
-        levels = len(mult)
-        att = sorted(int(2 ** i) for i in range(levels) if r.random() < 0.7)
-        # channels of the levels that carry attention (ds = 2^level in attention_resolutions) and of the middle block (always)
-        chs = {mc * mult[i] for i in range(levels) if 2 ** i in att} | {mc * mult[-1]}
-        heads = [h for h in ((1, 2, 3, 4, 6, 8, 12, 16) if WIDE else (1, 2, 4, 8)) if all(ch % h == 0 and ch // h in HEAD_DIMS for ch in chs)]
-        if mc * max(mult) <= (1280 if WIDE else 768) and heads:
-            break
-    cin, cout = (4, 4) if seed % 2 == 0 else (int(r.choice([1, 3, 8, 9, 16, 64])), int(r.choice([1, 3, 8, 64])))
-    cfg = dict(in_channels=cin, out_channels=cout, model_channels=mc, attention_resolutions=att, num_res_blocks=nrb, channel_mult=mult,
-               num_heads=int(r.choice(heads)), context_dim=int(r.choice([64, 128, 192, 320])))
-    q = 2 ** (levels - 1)
-    if WIDE:
-        H = int(r.choice([h for h in (8, 16, 24, 32, 40) if h % q == 0]))
-        W = int(r.choice([w for w in (8, 16, 24, 32, 40, 48, 64, 72, 96) if w % q == 0]))
-        if mc * max(mult) > 768 and H * W > 512:          # keep the CPU oracle in seconds
-            H, W = 8 if 8 % q == 0 else 16, 16
-        return cfg, dict(B=int(r.choice([1, 2, 3, 4, 5, 7])), H=H, W=W, T=int(r.choice([1, 2, 9, 31, 32, 33, 40])), seed=seed)
-    H = int(r.choice([h for h in (8, 16) if h % q == 0]))
-    W = int(r.choice([w for w in (16, 32, 64) if w % q == 0]))
-    return cfg, dict(B=int(r.choice([1, 2, 3])), H=H, W=W, T=int(r.choice([1, 9, 32])), seed=seed)
 
 
 @pytest.mark.parametrize("seed", fuzz_seeds(N_CASES))
@@ -64,35 +34,36 @@ def test_unet_configuration_product_vs_oracle(seed):
     import diff_foley_amd as P
     from diff_foley_amd import synth
     from oracle import unet as ou
-    cfg, o = _draw(seed)
-    cond = dict(origin_dim=64, embed_dim=cfg["context_dim"], seq_len=40)
-    sd = synth.make_state_dict(synth.state_dict_spec(cfg, synth.VAE_TINY, cond), 100 + seed)
+    k = fuzz_cases.unet_case(seed, WIDE)
+    cfg, o, cond, sd = k["cfg"], k["o"], k["cond"], k["sd"]
     m = P.LatentDiffusion(precision=PREC, **P.stage2_config(cfg, synth.VAE_TINY, cond))
     m.load_state_dict(sd)
     m.cuda()
     if TUNE:                      # exploratory: the in-plan autotuner walks its top candidates per GEMM (tiles the cost model does not pick)
         m.autotune(True)
     usd = ou.sub_state_dict(sd, "model.diffusion_model.")
-    g = torch.Generator().manual_seed(300 + seed)
-    B, H, W, T = o["B"], o["H"], o["W"], o["T"]
-    x = torch.randn(B, cfg["in_channels"], H, W, generator=g)
-    c = torch.randn(B, T, cfg["context_dim"], generator=g)
-    t = torch.randint(0, 1000, (B,), generator=g)
+    B = o["B"]
+    x, c, t, uc, tt = k["x"], k["c"], k["t"], k["uc"], k["tt"]
     ref = ou.unet_forward(usd, cfg, x, t, c)
     y = m.apply_model(x.cuda(), t.cuda(), c.cuda()).cpu()
     assert y.shape == ref.shape and torch.isfinite(y).all(), (cfg, o)
     err = rel_l2(y, ref)
     # classifier-free guidance through the fused entry point (one 2B-row plan, combine in the last GEMM's reduce / epilogue)
-    uc = 0.3 * torch.randn(B, T, cfg["context_dim"], generator=g)
-    tt = torch.full((B,), int(t[0]))
     e2 = ou.unet_forward(usd, cfg, torch.cat([x, x]), torch.cat([tt, tt]), torch.cat([uc, c]))
-    ref_cfg = e2[:B] + 3.0 * (e2[B:] - e2[:B])
+    ref_cfg = e2[:B] + fuzz_cases.UNET_CFG_SCALE * (e2[B:] - e2[:B])
     m.engine.set_context(torch.cat([uc, c]).cuda())
-    y_cfg = m.engine.unet_forward_cfg(x.cuda(), tt.float().cuda(), 3.0).cpu()
+    y_cfg = m.engine.unet_forward_cfg(x.cuda(), tt.float().cuda(), fuzz_cases.UNET_CFG_SCALE).cpu()
     err_cfg = rel_l2(y_cfg, ref_cfg)
     print(f"case {seed}: {cfg} {o} -> rel-L2 {err:.2e}, CFG {err_cfg:.2e}")
     assert err < TOL * PREC_SCALE, (cfg, o, err)
     assert err_cfg < 3 * TOL * PREC_SCALE, (cfg, o, err_cfg)          # guidance amplifies the (e_c - e_u) rounding by the scale
+    # ... and against the reference's own result on this case, by the same metric and bounds
+    rec = fuzz_record_for_run("unet", seed, dict(cfg=cfg, o=o), WIDE)
+    if rec is not None:
+        err_r, err_cfg_r = record_rel_l2(rec["y"], y), record_rel_l2(rec["y_cfg"], y_cfg)
+        print(f"case {seed}: against the reference's record -> rel-L2 {err_r:.2e}, CFG {err_cfg_r:.2e}")
+        assert err_r < TOL * PREC_SCALE, (cfg, o, err_r)
+        assert err_cfg_r < 3 * TOL * PREC_SCALE, (cfg, o, err_cfg_r)
 
 
 @pytest.mark.parametrize("mc,mult,H,W", [(256, [1, 2, 2, 4], 8, 16), (256, [1, 2, 2, 4], 8, 24), (192, [1, 2], 8, 8)])

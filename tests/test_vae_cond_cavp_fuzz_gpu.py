@@ -15,7 +15,8 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import fuzz_seeds, rel_l2
+import fuzz_cases
+from helpers import fuzz_record_for_run, fuzz_seeds, record_rel_l2, rel_l2
 
 pytestmark = pytest.mark.gpu
 
@@ -26,40 +27,19 @@ TUNE = os.environ.get("DF_FUZZ_TUNE", "0") != "0"
 WIDE = os.environ.get("DF_FUZZ_WIDE", "0") != "0"      # exploratory sweeps: wider spaces than the suite draws
 
 
-def _vae_draw(seed):
-    r = np.random.default_rng(6100 + seed)
-    if WIDE:
-        cfg = dict(z_channels=4, embed_dim=4, ch=int(r.choice([64, 128, 192])),
-                   ch_mult=[list(m) for m in ([1, 2], [1, 2, 2], [1, 2, 4], [1, 1, 2, 2], [1, 1], [1, 2, 4, 4], [1], [1, 3], [2, 2], [1, 1, 1],
-                                              [2, 1])][int(r.integers(0, 11))],
-                   num_res_blocks=int(r.choice([1, 2, 3, 4])), out_ch=int(r.choice([1, 2, 3, 4])))
-        H, W = [(4, 8), (8, 16), (16, 64), (8, 24), (16, 16), (1, 1), (3, 5), (5, 7), (1, 64), (6, 10), (2, 2), (12, 20)][int(r.integers(0, 12))]
-        if cfg["ch"] * max(cfg["ch_mult"]) >= 384 and H * W > 128:
-            H, W = 6, 10
-        return cfg, dict(B=int(r.choice([1, 2, 3, 5, 9, 17])) if H * W <= 64 else int(r.choice([1, 2, 3])), H=H, W=W)
-    cfg = dict(z_channels=4, embed_dim=4, ch=int(r.choice([64, 128])),
-               ch_mult=[list(m) for m in ([1, 2], [1, 2, 2], [1, 2, 4], [1, 1, 2, 2], [1, 1], [1, 2, 4, 4])][int(r.integers(0, 6))],
-               num_res_blocks=int(r.choice([1, 2, 3])), out_ch=int(r.choice([1, 3])))
-    H, W = [(4, 8), (8, 16), (16, 64), (8, 24), (16, 16)][int(r.integers(0, 5))]
-    if cfg["ch"] * max(cfg["ch_mult"]) >= 512 and H * W > 256:        # keep the CPU oracle in seconds
-        H, W = 8, 16
-    return cfg, dict(B=int(r.choice([1, 2, 3, 5])), H=H, W=W)
-
-
-@pytest.mark.parametrize("seed", fuzz_seeds(8))
+@pytest.mark.parametrize("seed", fuzz_seeds(fuzz_cases.N_CASES["vae"]))
 def test_vae_decoder_configuration_product_vs_oracle(seed):
     import diff_foley_amd as P
     from diff_foley_amd import synth
     from oracle import unet as ou, vae as ov
-    cfg, o = _vae_draw(seed)
-    sd = synth.make_state_dict(synth.state_dict_spec(synth.UNET_TINY, cfg, synth.COND_TINY), 700 + seed)
+    k = fuzz_cases.vae_case(seed, WIDE)
+    cfg, o, sd, z = k["cfg"], k["o"], k["sd"], k["z"]
     m = P.LatentDiffusion(precision=PREC, **P.stage2_config(synth.UNET_TINY, cfg, synth.COND_TINY))
     m.load_state_dict(sd)
     m.cuda()
     if TUNE:
         m.autotune(True)
     vsd = ou.sub_state_dict(sd, "first_stage_model.")
-    z = torch.randn(o["B"], 4, o["H"], o["W"], generator=torch.Generator().manual_seed(800 + seed))
     ref = ov.decode_first_stage(vsd, cfg, z)
     y = m.decode_first_stage(z.cuda()).cpu()
     up = 2 ** (len(cfg["ch_mult"]) - 1)
@@ -67,57 +47,58 @@ def test_vae_decoder_configuration_product_vs_oracle(seed):
     err = rel_l2(y, ref)
     print(f"vae case {seed}: {cfg} {o} -> rel-L2 {err:.2e}")
     assert err < 3e-3 * PREC_SCALE, (cfg, o, err)              # the full decoder measures 9.2e-4 on this build
+    rec = fuzz_record_for_run("vae", seed, dict(cfg=cfg, o=o), WIDE)          # ... and against the reference's own result on this case
+    if rec is not None:
+        err_r = record_rel_l2(rec["y"], y)
+        print(f"vae case {seed}: against the reference's record -> rel-L2 {err_r:.2e}")
+        assert err_r < 3e-3 * PREC_SCALE, (cfg, o, err_r)
 
 
-@pytest.mark.parametrize("seed", fuzz_seeds(6))
+@pytest.mark.parametrize("seed", fuzz_seeds(fuzz_cases.N_CASES["cond"]))
 def test_cond_stage_configuration_product_vs_oracle(seed):
     import diff_foley_amd as P
     from diff_foley_amd import synth
     from oracle import unet as ou, vae as ov
-    r = np.random.default_rng(6300 + seed)
-    cond = dict(origin_dim=int(r.choice([64, 128, 512])), embed_dim=int(r.choice([64, 128, 320, 768])), seq_len=int(r.choice([8, 40, 64])))
-    if WIDE:
-        cond = dict(origin_dim=int(r.choice([64, 128, 192, 512, 1024])), embed_dim=int(r.choice([64, 128, 192, 320, 768, 1024])),
-                    seq_len=int(r.choice([1, 2, 8, 33, 40, 64, 100])))
-    ucfg = dict(synth.UNET_TINY, context_dim=cond["embed_dim"])
-    sd = synth.make_state_dict(synth.state_dict_spec(ucfg, synth.VAE_TINY, cond), 900 + seed)
+    k = fuzz_cases.cond_case(seed, WIDE)
+    cond, ucfg, sd = k["cond"], k["ucfg"], k["sd"]
+    rec = fuzz_record_for_run("cond", seed, dict(cond=cond, calls=k["calls"]), WIDE)
     m = P.LatentDiffusion(precision="fp16", **P.stage2_config(ucfg, synth.VAE_TINY, cond))
     m.load_state_dict(sd)
     m.cuda()
     csd = ou.sub_state_dict(sd, "cond_stage_model.")
-    g = torch.Generator().manual_seed(950 + seed)
-    for T in sorted({1, int(r.integers(2, cond["seq_len"] + 1)) if cond["seq_len"] > 1 else 1, cond["seq_len"]}):
-        B = int(r.choice([1, 3, 4]))
-        f = torch.randn(B, T, cond["origin_dim"], generator=g)
+    for i, (call, f) in enumerate(zip(k["calls"], k["feats"])):
+        B, T = call["B"], call["T"]
         ref = ov.cond_stage(csd, f)
         c = m.get_learned_conditioning(f.cuda()).cpu()
         assert c.shape == ref.shape == (B, T, cond["embed_dim"])
         err = rel_l2(c, ref)
         print(f"cond case {seed}: {cond} B={B} T={T} -> rel-L2 {err:.2e}")
         assert err < 2e-3, (cond, B, T, err)
-    with pytest.raises(RuntimeError):             # longer than the positional table: the reference's broadcast add fails too
+        if rec is not None:                       # ... and against the reference's own result on this call
+            err_r = record_rel_l2(rec[f"c{i}"], c)
+            print(f"cond case {seed}: B={B} T={T} against the reference's record -> rel-L2 {err_r:.2e}")
+            assert err_r < 2e-3, (cond, B, T, err_r)
+    # longer than the positional table: the reference's embedding lookup fails (IndexError on the CPU, a device-side assert --
+    # RuntimeError -- on a GPU); the product's exception is both
+    with pytest.raises(RuntimeError) as ei:
         m.get_learned_conditioning(torch.randn(1, cond["seq_len"] + 1, cond["origin_dim"]).cuda())
+    if rec is not None:
+        assert rec["too_long_raises"] in [b.__name__ for b in type(ei.value).__mro__], (rec["too_long_raises"], type(ei.value).__mro__)
 
 
-@pytest.mark.parametrize("seed", fuzz_seeds(6))
+@pytest.mark.parametrize("seed", fuzz_seeds(fuzz_cases.N_CASES["cavp"]))
 def test_cavp_configuration_product_vs_oracle(seed):
     import diff_foley_amd as P
     from diff_foley_amd import synth
     from oracle import cavp as ocavp
-    r = np.random.default_rng(6500 + seed)
-    cfg = dict(stage_blocks=[int(v) for v in ([1, 1, 1, 1], [2, 1, 1, 1], [1, 2, 1, 2], [1, 1, 2, 1], [2, 2, 1, 1])[int(r.integers(0, 5))]],
-               base_channels=64, embed_dim=int(r.choice([64, 128, 512])))
-    sd = synth.make_state_dict(synth.cavp_spec(cfg), 1000 + seed)
+    k = fuzz_cases.cavp_case(seed, WIDE)
+    cfg, sd, v = k["cfg"], k["sd"], k["video"]
+    n, T, S = k["o"]["n"], k["o"]["T"], k["o"]["S"]
+    rec = fuzz_record_for_run("cavp", seed, dict(cfg=cfg, o=k["o"]), WIDE)
     m = P.CAVPInference(embed_dim=cfg["embed_dim"], stage_blocks=cfg["stage_blocks"], precision=PREC)
     missing, unexpected = m.load_state_dict(sd)
     assert not missing and not unexpected
     m.cuda()
-    n, T, S = int(r.choice([1, 2, 3])), int(r.choice([1, 2, 5, 9])), int(r.choice([64, 96, 160]))
-    if WIDE:
-        n, T, S = int(r.choice([1, 2, 3, 5])), int(r.choice([1, 2, 3, 5, 9, 16, 17])), int(r.choice([32, 64, 96, 128, 160, 224]))          # multiples of 32: df_cavp_encode refuses other frame sizes (the path resizes to 224)
-        if T * S * S * n > 9 * 160 * 160 * 3:
-            n = 1
-    v = synth.synthetic_video(n, T, S, seed=1100 + seed)
     for normalize in (True, False):
         ref = ocavp.encode_video(sd, v, normalize=normalize, stage_blocks=tuple(cfg["stage_blocks"]))
         f = m.encode_video(v.cuda(), normalize=normalize, pool=False).cpu()
@@ -126,6 +107,13 @@ def test_cavp_configuration_product_vs_oracle(seed):
         cos = torch.nn.functional.cosine_similarity(f, ref, dim=-1).min().item()
         print(f"cavp case {seed}: {cfg} clips={n} frames={T} size={S} normalize={normalize} -> rel-L2 {err:.2e}, min cos {cos:.6f}")
         assert err < 2e-3 * PREC_SCALE and cos > 1 - 1e-5 * PREC_SCALE ** 2, (cfg, n, T, S, err, cos)
+        if rec is not None:                       # ... and against the reference's own features on this case
+            stored = rec["feats" if normalize else "feats_raw"]
+            f_rec = torch.from_numpy(stored["full"])
+            err_r = record_rel_l2(stored, f)
+            cos_r = torch.nn.functional.cosine_similarity(f, f_rec, dim=-1).min().item()
+            print(f"cavp case {seed}: normalize={normalize} against the reference's record -> rel-L2 {err_r:.2e}, min cos {cos_r:.6f}")
+            assert err_r < 2e-3 * PREC_SCALE and cos_r > 1 - 1e-5 * PREC_SCALE ** 2, (cfg, n, T, S, err_r, cos_r)
 
 
 @pytest.mark.parametrize("H,W", [(2, 8), (4, 8), (4, 24), (8, 20)])
