@@ -199,6 +199,57 @@ int df_cavp_pool(const float* feat, float* out, int B, int T, int C, int kernel,
   });
 }
 
+int df_config_cavp_spec(df_ctx* c, const df_cavp_spec_config* cfg) {
+  return guard([&] {
+    if (!cfg) fail("cavp spec: null configuration");
+    c->scfg = *cfg;
+    c->has_cavp_spec = true;
+  });
+}
+
+// T' of a T-frame mel: four floor-halvings (the (2, 2) pools of conv_block1 .. 4)
+static int cavp_spec_rows(int T) { return T / 2 / 2 / 2 / 2; }
+
+// clips per plan: the widest operand (conv_block1's full-resolution map) stays far below the 2 GiB operand addressing
+static int cavp_spec_chunk(const df_ctx* c, int T, int n_mels) {
+  const size_t per_clip = (size_t)T * n_mels * (size_t)std::max(c->scfg.channels[0], 1) * 2;
+  const int chunk = (int)std::max<size_t>(1, ((size_t)1 << 30) / std::max<size_t>(per_clip, 1));
+  return std::min(chunk, 16);
+}
+
+static void cavp_spec_check(df_ctx* c, const char* what, int B, int n_mels, int T) {
+  if (!c->has_cavp_spec) fail("cavp spectrogram encoder not configured (df_config_cavp_spec, with the spec_encoder tensors loaded)");
+  need_positive(what, {{"clips", B}, {"mel bins", n_mels}, {"frames", T}});
+  if (n_mels != c->scfg.n_mels) fail("%s: the mel has %d bins, the encoder is configured for %d", what, n_mels, c->scfg.n_mels);
+  if (cavp_spec_rows(T) < 1) fail("%s: %d frames give no output row (16 frames make one)", what, T);
+}
+
+int df_cavp_spec_encode(df_ctx* c, const float* spec, float* out, int B, int n_mels, int T, int normalize, void* stream) {
+  return guard([&] {
+    cavp_spec_check(c, "cavp spec", B, n_mels, T);
+    need_pointers("cavp spec", {{"spec", spec}, {"out", out}});
+    const int chunk = cavp_spec_chunk(c, T, n_mels), To = cavp_spec_rows(T);
+    for (int b0 = 0; b0 < B; b0 += chunk) {
+      const int nb = std::min(chunk, B - b0);
+      Plan* p = get_plan(c, keyf("cavpspec_%d_%d_%d", nb, T, n_mels), [&](Plan* pl) { build_cavp_spec(c, pl, nb, T, n_mels); });
+      RunArgs a;
+      a.x = spec + (size_t)b0 * n_mels * T;
+      a.out = out + (size_t)b0 * To * c->scfg.embed_dim;
+      a.scale = normalize ? 1.f : 0.f;
+      run_ops(c, p, 0, p->ops.size(), (hipStream_t)stream, a);
+    }
+  });
+}
+
+int df_cavp_similarity(const float* v, const float* s, float* out, int Bv, int Bs, int T, int D, float scale, void* stream) {
+  return guard([&] {
+    need_positive("cavp similarity", {{"video clips", Bv}, {"audio clips", Bs}, {"frames", T}, {"feature width", D}});
+    need_pointers("cavp similarity", {{"v", v}, {"s", s}, {"out", out}});
+    if (D % 4) fail("cavp similarity: feature width %d is not a multiple of 4", D);
+    HIPCHK(launch_cavp_similarity(v, s, out, Bv, Bs, T, D, scale, (hipStream_t)stream));
+  });
+}
+
 int df_cond_encode(df_ctx* c, const float* feats, float* out, int B, int T, void* stream) {
   return guard([&] {
     if (!c->has_cond) fail("cond stage not configured");

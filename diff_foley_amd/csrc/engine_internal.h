@@ -16,7 +16,8 @@
 // Builder, and the prototypes of every function one unit calls in another.  Who defines what:
 //   engine_pack.hip      df_ctx packers
 //   engine_builder.hip   choose_tile, Builder members
-//   engine_nets.hip      UNet topology, build_emb_table, build_unet_like, build_vae, build_vae_encoder, build_cond, build_cavp
+//   engine_nets.hip      UNet topology, build_emb_table, build_unet_like, build_vae, build_vae_encoder, build_cond, build_cavp,
+//                        build_cavp_spec
 //   engine_cls_grad.hip  build_classifier_grad
 //   engine_run.hip       finish_plan, run_ops (+ debug hooks), get_plan, keyf
 //   engine_tune.hip      tune cache, apply_tune_cache, autotune_plan
@@ -229,8 +230,10 @@ struct __attribute__((visibility("hidden"))) df_ctx {
   std::map<std::string, dfe::RawT> raw;
   std::map<std::string, void*> packed;
   std::vector<void*> packed_blocks;
-  bool has_unet = false, has_vae = false, has_cond = false, has_cls = false, has_cavp = false, has_vae_enc = false, finalized = false;
+  bool has_unet = false, has_vae = false, has_cond = false, has_cls = false, has_cavp = false, has_vae_enc = false, has_cavp_spec = false,
+       finalized = false;
   df_cavp_config pcfg{};
+  df_cavp_spec_config scfg{};
   df_unet_config ucfg{}, ccfg{};
   df_vae_config vcfg{};
   df_vae_encoder_config ecfg{};
@@ -341,6 +344,8 @@ struct __attribute__((visibility("hidden"))) df_ctx {
   // Conv3d + eval BatchNorm3d of an mmcv ConvModule `p` (keys p.conv.weight, p.bn.*): operand [O][kp] with the BN scale
   // folded in (k = tap*I + i, zero padded to kp) and the fp32 bias beta - mean*scale.
   void w_conv3d_bn(const std::string& p, int kp, const bf16_t** w, const float** b);
+  // Conv2d 3x3 (no bias) `conv`.weight + eval BatchNorm2d `bn`.* of a Cnn14 ConvBlock: the same fold, operand [O][9 I] (k = tap*I + i)
+  void w_conv2d_bn(const std::string& conv, const std::string& bn, int kp, const bf16_t** w, const float** b);
   // LayerNorm `norm` folded into the Linear(s) `names` stacked along the output dim (biases[i] may be empty):
   // operand rows gamma*W, their column sums and the folded bias beta.W + b.  geglu: ONE matrix, rows GEGLU-interleaved.
   void w_ln_stack(const std::string& key, const std::string& norm, const std::vector<std::string>& names,
@@ -484,6 +489,9 @@ void build_vae_encoder(df_ctx* c, Plan* pl, int B, int H, int W, int tap = -1);
 std::vector<std::string> vae_encoder_tensor_names(const df_ctx* c);
 void build_cond(df_ctx* c, Plan* pl, int B, int T);
 void build_cavp(df_ctx* c, Plan* pl, int T, int H, int W);
+// CAVP spectrogram encoder (Cnn14) over B clips of T frames x n_mels; tap 1 .. 6 (df_test_cavp_spec_tap): that ConvBlock's output is also
+// copied to RunArgs.out2 as the plan holds it (operand type behind the pools of blocks 1 .. 5, fp32 for block 6)
+void build_cavp_spec(df_ctx* c, Plan* pl, int B, int T, int n_mels, int tap = -1);
 
 // ---- plan execution and the plan cache (engine_run.hip)
 void finish_plan(df_ctx* c, Plan* pl);

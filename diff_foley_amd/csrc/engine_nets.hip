@@ -1,5 +1,5 @@
 // libdfengine: UNet topology and the forward plans of the four networks -- UNet / classifier backbone, VAE decoder, cond stage,
-// VAE encoder, CAVP video encoder (types and the Builder: engine_internal.h).
+// VAE encoder, CAVP video encoder, CAVP spectrogram encoder (types and the Builder: engine_internal.h).
 #include "engine_internal.h"
 
 DFE_NAMESPACE {
@@ -791,6 +791,126 @@ void build_cavp(df_ctx* c, Plan* pl, int T, int H, int W) {
       return a.scale != 0.f ? launch_l2norm_rows(a.out, F, E, s) : hipSuccess;     // a.scale doubles as the normalize flag
     });
   }
+}
+
+// CAVP spectrogram encoder: Cnn14 over B clips of T frames x n_mels mel bins -> [B*T'][embed] features, T' = T floor-halved four times.
+// inference/model/cavp_model.py:68-84 (encode_spec, pool=False), cavp_modules.py:1440-1483 (ConvBlock) / 1516-1546 (Cnn14.forward).
+// Activations are NHWC with H = time, W = mel.  conv_block1.conv1 (one input channel, input BatchNorm in front of the padding) is the
+// VALU kernel spec_conv_in; the other eleven convs are implicit GEMMs with the eval BatchNorm folded into weights + bias and ReLU in
+// the epilogue.  The second conv of a block writes fp32 and the avg-pool behind it rounds to the operand type, so an activation is
+// rounded once; block 6's (1, 1) pool is no launch, the head pool reads its fp32 output.  fc1 runs twice on one packed weight
+// (cavp_modules.py:1543-1544).  Every GEMM choice is made for the per-sample problem: a clip's features do not depend on its batch.
+void build_cavp_spec(df_ctx* c, Plan* pl, int B, int T, int n_mels, int tap) {
+  const df_cavp_spec_config& k = c->scfg;
+  const std::string pre = "cavp.spec_encoder.";
+  Builder b{c, pl, pre, 0};
+  b.choice_NB = B;
+  pl->fixed_choices = true;
+  const int C1 = k.channels[0];
+  if (C1 < 8 || C1 % 8 || C1 > 256) fail("cavp spec: channels[0] = %d: the first conv is built for 8 .. 256 channels in steps of 8", C1);
+  if (k.fc_dim != k.channels[5])
+    fail("cavp spec: fc_dim = %d, channels[5] = %d: fc1 is applied twice (cavp_modules.py:1543-1544), so it must be square", k.fc_dim,
+         k.channels[5]);
+  if ((int)c->rt(pre + "bn.weight").n != n_mels) fail("cavp spec: the input BatchNorm has %zu bins, the mel has %d", c->rt(pre + "bn.weight").n, n_mels);
+  auto bn4 = [&](const std::string& p) {
+    return std::array<const float*, 4>{c->f32(p + ".weight"), c->f32(p + ".bias"), c->f32(p + ".running_mean"), c->f32(p + ".running_var")};
+  };
+  auto tap_here = [&](int id, const void* src, size_t bytes) {      // tests only
+    if (tap != id) return;
+    b.other("cavpspec.tap", [=](hipStream_t s, const RunArgs& ra) {
+      return ra.out2 ? hipMemcpyAsync(ra.out2, src, bytes, hipMemcpyDeviceToDevice, s) : hipSuccess;
+    });
+  };
+  int h = T, w = n_mels;
+  bf16_t* h1 = b.buf<bf16_t>((size_t)B * h * w * C1);
+  {
+    const std::array<const float*, 4> bn0 = bn4(pre + "bn"), bn1 = bn4(pre + "conv_block1.bn1");
+    const float* wi = c->f32(pre + "conv_block1.conv1.weight");
+    if (c->rt(pre + "conv_block1.conv1.weight").n != (size_t)C1 * 9) fail("cavp spec: conv_block1.conv1.weight is not [%d][1][3][3]", C1);
+    pl->ext_hint = std::max(pl->ext_hint, (size_t)B * n_mels * T * 4);
+    b.other("cavpspec.conv_in", [=](hipStream_t s, const RunArgs& a) {
+      return launch_spec_conv_in(a.x, bn0.data(), wi, bn1.data(), 1e-5f, h1, C1, B, n_mels, T, C1, s);
+    });
+    b.emits(h1, (long)B * h * w, C1, C1);
+  }
+  const bf16_t* wp;
+  const float* bias;
+  bf16_t* xb = nullptr;            // operand-type input of the block (blocks 2 .. 6)
+  float* f = nullptr;              // fp32 output of the block's second conv
+  int cin = 1;
+  for (int blk = 0; blk < 6; ++blk) {
+    const int co = k.channels[blk];
+    const std::string p = pre + "conv_block" + std::to_string(blk + 1);
+    if (blk > 0) {
+      h1 = b.buf<bf16_t>((size_t)B * h * w * co);
+      c->w_conv2d_bn(p + ".conv1", p + ".bn1", 9 * cin, &wp, &bias);
+      GemmParams g = Builder::gp_conv3(xb, B, h, w, cin, wp, co, 1, 0);
+      Builder::out_b16(g, h1, co);
+      g.bias = bias;
+      g.relu = 1;
+      b.gemm(g, 1, "cavpspec.conv1");
+      pl->release(xb);
+    }
+    f = b.buf<float>((size_t)B * h * w * co);
+    {
+      c->w_conv2d_bn(p + ".conv2", p + ".bn2", 9 * co, &wp, &bias);
+      GemmParams g = Builder::gp_conv3(h1, B, h, w, co, wp, co, 1, 0);
+      Builder::out_f32(g, f, co);
+      g.bias = bias;
+      g.relu = 1;
+      b.gemm(g, 1, "cavpspec.conv2");
+    }
+    pl->release(h1);
+    cin = co;
+    if (blk == 5) break;           // avg_pool2d((1, 1)) is the identity
+    const int ph = blk < 4 ? 2 : 1, pw = 2;
+    if (h < ph || w < pw) fail("cavp spec: the %dx%d map of conv_block%d does not survive its (%d, %d) pool (%d frames x %d mels)", h, w, blk + 1, ph, pw, T, n_mels);
+    const int oh = h / ph, ow = w / pw;
+    xb = b.buf<bf16_t>((size_t)B * oh * ow * co);
+    {
+      const float* src = f;
+      bf16_t* dst = xb;
+      const int hh = h, ww = w;
+      b.other("cavpspec.pool", [=](hipStream_t s, const RunArgs&) { return launch_avgpool_nhwc(src, co, dst, co, B, hh, ww, co, ph, pw, s); });
+      b.emits(xb, (long)B * oh * ow, co, co);
+    }
+    pl->release(f);
+    h = oh;
+    w = ow;
+    tap_here(blk + 1, xb, (size_t)B * h * w * co * sizeof(bf16_t));
+  }
+  tap_here(6, f, (size_t)B * h * w * cin * sizeof(float));
+  // ---- head: mean over mel, max3 + avg3 over time, relu(fc1) twice, final_project (+ L2 normalisation when asked)
+  const int rows = B * h, C6 = cin, E = k.embed_dim;
+  bf16_t* pooled = b.buf<bf16_t>((size_t)rows * C6);
+  {
+    const float* src = f;
+    const int hh = h, ww = w;
+    b.other("cavpspec.head_pool", [=](hipStream_t s, const RunArgs&) { return launch_spec_head_pool(src, C6, pooled, C6, B, hh, ww, C6, s); });
+    b.emits(pooled, rows, C6, C6);
+  }
+  pl->release(f);
+  const bf16_t* wf = c->w_linear(pre + "fc1.weight");
+  const float* bf = c->f32(pre + "fc1.bias");
+  bf16_t* y1 = b.buf<bf16_t>((size_t)rows * C6);
+  bf16_t* y2 = b.buf<bf16_t>((size_t)rows * C6);
+  for (int i = 0; i < 2; ++i) {
+    GemmParams g = Builder::gp_linear(i ? y1 : pooled, rows, C6, wf, C6);
+    Builder::out_b16(g, i ? y2 : y1, C6);
+    g.bias = bf;
+    g.relu = 1;
+    b.gemm(g, 1, i ? "cavpspec.fc1b" : "cavpspec.fc1a");
+  }
+  {
+    GemmParams g = Builder::gp_linear(y2, rows, C6, c->w_linear(pre + "final_project.weight"), E);
+    Builder::out_f32(g, nullptr, E);
+    g.bias = c->f32(pre + "final_project.bias");
+    Op& o = b.gemm(g, 1, "cavpspec.project");
+    o.c_ext = true;
+  }
+  b.other("cavpspec.l2norm", [=](hipStream_t s, const RunArgs& a) {      // a.scale doubles as the normalize flag, as in build_cavp
+    return a.scale != 0.f ? launch_l2norm_rows(a.out, rows, E, s) : hipSuccess;
+  });
 }
 
 void build_emb_table(df_ctx* c, int which) {

@@ -142,6 +142,22 @@ void df_ctx::w_conv3d_bn(const std::string& p, int kp, const bf16_t** w, const f
   *b = (const float*)blk[1];
 }
 
+void df_ctx::w_conv2d_bn(const std::string& conv, const std::string& bn, int kp, const bf16_t** w, const float** b) {
+  const std::string kw = "c2d:" + conv + ":" + std::to_string(kp);
+  const auto blk = pack_once<2>({kw, kw + ":b"}, [&]() -> std::array<void*, 2> {
+    const RawT& t = rt(conv + ".weight");
+    if (t.shape.size() != 4 || t.shape[2] != 3 || t.shape[3] != 3) fail("'%s.weight' is not a 3x3 conv weight", conv.c_str());
+    const int O = (int)t.shape[0], I = (int)t.shape[1];
+    bf16_t* wo = (bf16_t*)pmalloc((size_t)O * kp * 2);
+    float* bo = (float*)pmalloc((size_t)O * 4);
+    HIPCHK(launch_pack_conv3d_bn(f32(conv + ".weight"), f32(bn + ".weight"), f32(bn + ".bias"), f32(bn + ".running_mean"),
+                                 f32(bn + ".running_var"), 1e-5f, wo, bo, O, I, 1, 3, 3, kp, pack_stream));
+    return {wo, bo};
+  });
+  *w = (const bf16_t*)blk[0];
+  *b = (const float*)blk[1];
+}
+
 void df_ctx::w_ln_stack(const std::string& key, const std::string& norm, const std::vector<std::string>& names,
                         const std::vector<std::string>& biases, bool geglu, const bf16_t** w, const float** cs, const float** bb) {
   const auto blk = pack_once<3>({key + "#lnw", key + "#lncs", key + "#lnbb"}, [&]() -> std::array<void*, 3> {

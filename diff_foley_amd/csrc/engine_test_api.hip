@@ -591,6 +591,22 @@ int df_test_vae_encode_tap(df_ctx* c, const float* x, float* moments, float* tap
   });
 }
 
+int df_test_cavp_spec_tap(df_ctx* c, const float* spec, float* out, void* tap_out, int tap, int B, int n_mels, int T, int normalize,
+                          void* stream) {
+  return guard([&] {
+    if (!c->has_cavp_spec) fail("cavp spectrogram encoder not configured");
+    if (B <= 0 || B > 16 || n_mels != c->scfg.n_mels || T < 16 || tap < 1 || tap > 6)
+      fail("cavp spec tap: bad shape %d x %d x %d / tap %d", B, n_mels, T, tap);
+    Plan* p = get_plan(c, keyf("cavpspec_tap%d_%d_%d_%d", tap, B, T, n_mels), [&](Plan* pl) { build_cavp_spec(c, pl, B, T, n_mels, tap); });
+    RunArgs a;
+    a.x = spec;
+    a.out = out;
+    a.out2 = (float*)tap_out;
+    a.scale = normalize ? 1.f : 0.f;
+    run_ops(c, p, 0, p->ops.size(), (hipStream_t)stream, a);
+  });
+}
+
 static GemmParams test_down_params(const uint16_t* A, const uint16_t* W, const float* bias, float* C, int NB, int H, int Wd, int Cin,
                                    int Cout, int pad, int splitk) {
   if (pad != 0 && pad != 1) fail("conv3x3_down: pad %d", pad);
@@ -800,6 +816,16 @@ int df_test_maxpool_time(const float* x, float* out, int B, int T, int C, int k,
 }
 int df_test_l2norm_rows(float* x, int rows, int C, void* stream) {
   DF_TEST_LAUNCH(launch_l2norm_rows(x, rows, C, (hipStream_t)stream));
+}
+int df_test_spec_conv_in(const float* spec, const float* const* bn0, const float* w, const float* const* bn1, float eps, uint16_t* out,
+                         int ldo, int B, int n_mels, int T, int C1, void* stream) {
+  DF_TEST_LAUNCH(launch_spec_conv_in(spec, bn0, w, bn1, eps, out, ldo, B, n_mels, T, C1, (hipStream_t)stream));
+}
+int df_test_avgpool_nhwc(const float* x, int ldx, uint16_t* out, int ldo, int B, int H, int W, int C, int ph, int pw, void* stream) {
+  DF_TEST_LAUNCH(launch_avgpool_nhwc(x, ldx, out, ldo, B, H, W, C, ph, pw, (hipStream_t)stream));
+}
+int df_test_spec_head_pool(const float* x, int ldx, uint16_t* out, int ldo, int B, int T, int W, int C, void* stream) {
+  DF_TEST_LAUNCH(launch_spec_head_pool(x, ldx, out, ldo, B, T, W, C, (hipStream_t)stream));
 }
 #undef DF_TEST_LAUNCH
 

@@ -198,6 +198,22 @@ hipError_t launch_pack_conv3d_bn(const float* w, const float* gamma, const float
 hipError_t launch_maxpool_time(const float* x, float* out, int B, int T, int C, int k, hipStream_t s);
 hipError_t launch_l2norm_rows(float* x, int rows, int C, hipStream_t s);
 
+// ---- CAVP spectrogram encoder, Cnn14 (csrc/cavp_spec.hip; cavp_model.py:68-84, cavp_modules.py:1440-1546) ------
+// The first conv of the tower from the caller's mel: spec fp32 [B][NM][T] -> operand type NHWC [B][T][NM][ldo >= C1] =
+// ReLU(bn1(conv3x3(pad0(bn0(spec^T))))).  bn0 (over the NM mel bins) and bn1 (over the C1 channels) = {weight, bias, running_mean,
+// running_var}; bn0 is applied before the zero padding; w [C1][1][3][3] (ky = time, kx = mel).  C1 % 8 == 0, C1 <= 256, ldo % 8 == 0.
+hipError_t launch_spec_conv_in(const float* spec, const float* const bn0[4], const float* w, const float* const bn1[4], float eps,
+                               uint16_t* out, int ldo, int B, int NM, int T, int C1, hipStream_t s);
+// F.avg_pool2d((ph, pw)), (ph, pw) = (2, 2) or (1, 2), floor semantics: fp32 NHWC [B][H][W][ldx] -> operand type
+// [B][H/ph][W/pw][ldo].  C % 8 == 0, ldx % 4 == 0, ldo % 8 == 0.
+hipError_t launch_avgpool_nhwc(const float* x, int ldx, uint16_t* out, int ldo, int B, int H, int W, int C, int ph, int pw,
+                               hipStream_t s);
+// Cnn14's head in front of fc1: fp32 [B][T][W][ldx] -> mean over W, then max_pool1d(3, 1, 1) + avg_pool1d(3, 1, 1) along T inside
+// each clip -> operand-type rows [B*T][ldo].  C % 4 == 0, ldx % 4 == 0, ldo % 4 == 0.
+hipError_t launch_spec_head_pool(const float* x, int ldx, uint16_t* out, int ldo, int B, int T, int W, int C, hipStream_t s);
+// out[i][j] = scale * mean_t <v[i][t][:], sf[j][t][:]>: v [Bv][T][D], sf [Bs][T][D], out [Bv][Bs], all fp32; D % 4 == 0.
+hipError_t launch_cavp_similarity(const float* v, const float* sf, float* out, int Bv, int Bs, int T, int D, float scale, hipStream_t s);
+
 // Frame pre-processing in front of the CAVP encoder (Extract_CAVP_Features.forward, demo_util.py:100-104, 150-151):
 // frames uint8 [T][H][W][3] RGB -> float [T][3][OH][OW] in [0,1] = torchvision Resize((OH,OW)) on a PIL image
 // (PIL.Image.resize BILINEAR, antialiased, 8-bit fixed point) + ToTensor(), bit-identical to Pillow.

@@ -104,6 +104,10 @@ class CavpConfig(C.Structure):
     _fields_ = [("stage_blocks", C.c_int * 4), ("base_channels", C.c_int), ("embed_dim", C.c_int)]
 
 
+class CavpSpecConfig(C.Structure):
+    _fields_ = [("n_mels", C.c_int), ("channels", C.c_int * 6), ("fc_dim", C.c_int), ("embed_dim", C.c_int)]
+
+
 _libs = {}
 
 _SIGS = {
@@ -115,6 +119,9 @@ _SIGS = {
     "df_config_cavp": [C.c_void_p, C.POINTER(CavpConfig)],
     "df_cavp_encode": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p],
     "df_cavp_pool": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p],
+    "df_config_cavp_spec": [C.c_void_p, C.POINTER(CavpSpecConfig)],
+    "df_cavp_spec_encode": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p],
+    "df_cavp_similarity": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p],
     "df_config_classifier": [C.c_void_p, C.POINTER(UNetConfig)],
     "df_load_tensor": [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int],
     "df_load_tensor_dev": [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int],
@@ -247,6 +254,11 @@ _SIGS = {
     "df_test_pack_conv3d_bn": [C.c_void_p] * 5 + [C.c_float, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p],
     "df_test_maxpool_time": [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p],
     "df_test_l2norm_rows": [C.c_void_p, C.c_int, C.c_int, C.c_void_p],
+    "df_test_spec_conv_in": [C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(C.c_void_p), C.c_float, C.c_void_p] + [C.c_int] * 5
+                            + [C.c_void_p],
+    "df_test_avgpool_nhwc": [C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p],
+    "df_test_spec_head_pool": [C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p],
+    "df_test_cavp_spec_tap": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p],
     "df_test_peak": [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p],
     "df_test_fill": [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_void_p],
 }
@@ -471,17 +483,86 @@ class Engine:
     def cavp_encode_pooled(self, video, normalize=True, kernel=16):
         """encode_video(pool=True) (cavp_model.py:58-59): MaxPool1d(16) over the frames of the projected features, then the
         optional L2 normalisation; (B, T // 16, embed), squeezed to (B, embed) for one window like the reference's squeeze(2)."""
-        feat = self.cavp_encode(video, normalize=False)
+        return self.cavp_pool(self.cavp_encode(video, normalize=False), normalize, "encode_video", "frames", kernel)
+
+    def cavp_pool(self, feat, normalize, what, rows, kernel=16):
+        """The contrastive head of either tower on un-normalised features (B, T, C) (cavp_model.py:58-63, 77-82): MaxPool1d(kernel)
+        over the rows, then the optional L2 normalisation -- df_cavp_pool.  ``what`` / ``rows`` name the caller in the messages."""
         B, T, Cc = feat.shape
         if T < kernel:
-            raise RuntimeError(f"encode_video(pool=True): {T} frames are fewer than the MaxPool1d window of {kernel}")
+            raise RuntimeError(f"{what}(pool=True): {T} {rows} are fewer than the MaxPool1d window of {kernel}")
         if normalize and T // kernel > 1:
             # F.normalize(dim=-1) then runs over the WINDOW axis of the reference's (B, C, T // 16) tensor (squeeze(2) is a no-op
             # there) -- a shape the contrastive head is never used with; refused rather than guessed
-            raise NotImplementedError("encode_video(pool=True, normalize=True) is defined for one 16-frame window (16..31 frames)")
+            raise NotImplementedError(f"{what}(pool=True, normalize=True) is defined for one {kernel}-row window ({kernel}..{2 * kernel - 1} "
+                                      f"{rows}): the reference normalises across the windows there")
         out = torch.empty(B, T // kernel, Cc, device=self.device, dtype=torch.float32)
-        _chk(self.L.df_cavp_pool(_ptr(feat), _ptr(out), B, T, Cc, kernel, int(bool(normalize)), _stream()), self.L)
+        if out.numel():
+            _chk(self.L.df_cavp_pool(_ptr(feat), _ptr(out), B, T, Cc, kernel, int(bool(normalize)), _stream()), self.L)
         return out[:, 0] if out.shape[1] == 1 else out.permute(0, 2, 1)      # reference layout before squeeze(2): (B, C, T/16)
+
+    def config_cavp_spec(self, cfg):
+        """cfg: dict(n_mels, channels[6], fc_dim, embed_dim) -- synth.CAVP_AUDIO_FULL is the reference's Cnn14."""
+        k = CavpSpecConfig(int(cfg["n_mels"]), (C.c_int * 6)(*[int(v) for v in cfg["channels"]]), int(cfg["fc_dim"]),
+                           int(cfg["embed_dim"]))
+        self.cavp_spec_cfg = dict(cfg)
+        _chk(self.L.df_config_cavp_spec(self._h, C.byref(k)), self.L)
+
+    @staticmethod
+    def cavp_spec_rows(frames):
+        """Output rows of a ``frames``-long mel: four floor-halvings (the (2, 2) pools of conv_block1 .. 4)."""
+        return int(frames) // 2 // 2 // 2 // 2
+
+    def _cavp_spec_input(self, spec):
+        cfg = getattr(self, "cavp_spec_cfg", None)
+        if cfg is None:
+            raise RuntimeError("cavp_spec_encode: the spectrogram encoder is not configured (config_cavp_spec)")
+        spec = _dev_f32(spec, self.device)
+        if spec.ndim != 3:
+            raise RuntimeError(f"encode_spec: spec must be (B, n_mels, T), got shape {tuple(spec.shape)}")
+        B, M, T = spec.shape
+        if M != cfg["n_mels"]:
+            raise RuntimeError(f"encode_spec: spec has {M} mel bins, the encoder's input BatchNorm has {cfg['n_mels']}")
+        if self.cavp_spec_rows(T) < 1:
+            raise RuntimeError(f"encode_spec: {T} frames give no output row (the four (2, 2) pools need at least 16)")
+        return spec
+
+    def cavp_spec_encode(self, spec, normalize=False):
+        """spec (B, n_mels, T) fp32 normalised log-mel -> (B, T // 16, embed) (CAVP_Inference.encode_spec, pool=False)."""
+        spec = self._cavp_spec_input(spec)
+        B, M, T = spec.shape
+        out = torch.empty(B, self.cavp_spec_rows(T), self.cavp_spec_cfg["embed_dim"], device=self.device, dtype=torch.float32)
+        if B == 0:                # no clips: an empty result, like the reference's conv stack on an empty batch
+            return out
+        _chk(self.L.df_cavp_spec_encode(self._h, _ptr(spec), _ptr(out), B, M, T, int(bool(normalize)), self._on("cavpspec")), self.L)
+        return out
+
+    def cavp_spec_encode_tap(self, spec, tap, normalize=False):
+        """Tests: (features, one ConvBlock's output as fp32 NCHW (B, C, t, mel)) -- df_test_cavp_spec_tap, tap 1 .. 6."""
+        spec = self._cavp_spec_input(spec)
+        B, M, T = spec.shape
+        out = torch.empty(B, self.cavp_spec_rows(T), self.cavp_spec_cfg["embed_dim"], device=self.device, dtype=torch.float32)
+        h, w = T, M
+        for i in range(min(tap, 5)):
+            h, w = (h // 2 if i < 4 else h), w // 2
+        ch = self.cavp_spec_cfg["channels"][tap - 1]
+        stage = torch.empty(B, h, w, ch, device=self.device, dtype=torch.float32 if tap == 6 else self.operand_dtype)
+        _chk(self.L.df_test_cavp_spec_tap(self._h, _ptr(spec), _ptr(out), _ptr(stage), int(tap), B, M, T, int(bool(normalize)),
+                                          self._on("cavpspec")), self.L)
+        return out, stage.float().permute(0, 3, 1, 2).contiguous()
+
+    def cavp_similarity(self, v, s, scale=1.0):
+        """out[i][j] = scale * mean_t <v[i,t,:], s[j,t,:]> for v (Bv, T, D), s (Bs, T, D) -> (Bv, Bs) (df_cavp_similarity)."""
+        v, s = _dev_f32(v, self.device), _dev_f32(s, self.device)
+        if v.ndim != 3 or s.ndim != 3 or v.shape[1:] != s.shape[1:]:
+            raise RuntimeError(f"cavp_similarity: features must be (Bv, T, D) and (Bs, T, D) with the same T and D, got "
+                               f"{tuple(v.shape)} and {tuple(s.shape)}")
+        out = torch.empty(v.shape[0], s.shape[0], device=self.device, dtype=torch.float32)
+        if out.numel() == 0:
+            return out
+        _chk(self.L.df_cavp_similarity(_ptr(v), _ptr(s), _ptr(out), v.shape[0], s.shape[0], v.shape[1], v.shape[2], float(scale),
+                                       _stream()), self.L)
+        return out
 
     def load_tensor(self, name, t):
         shape = (C.c_int64 * t.dim())(*t.shape)

@@ -256,6 +256,50 @@ def synthetic_video(batch, frames=32, size=224, seed=77):
     return (out + 0.5).clamp_(0, 1)
 
 
+CAVP_AUDIO_FULL = dict(n_mels=128, channels=[64, 128, 256, 512, 1024, 2048], fc_dim=2048, embed_dim=512)
+CAVP_AUDIO_TINY = dict(n_mels=64, channels=[64, 64, 128, 128, 256, 256], fc_dim=256, embed_dim=64)
+
+
+def cavp_audio_spec(cfg=CAVP_AUDIO_FULL):
+    """CAVP_Inference.state_dict() keys of the spectrogram branch: Cnn14 (inference/model/cavp_modules.py:1440-1465, 1487-1507) and
+    the logit scale (inference/model/cavp_model.py:43); spec_project_head is an Identity and has no parameters."""
+    spec = OrderedDict()
+
+    def bn(p, c):
+        for n in ("weight", "bias", "running_mean", "running_var"):
+            spec[p + "." + n] = (c,)
+    bn("spec_encoder.bn", cfg["n_mels"])
+    cin = 1
+    for i, co in enumerate(cfg["channels"]):
+        p = f"spec_encoder.conv_block{i + 1}"
+        spec[p + ".conv1.weight"] = (co, cin, 3, 3)
+        spec[p + ".conv2.weight"] = (co, co, 3, 3)
+        bn(p + ".bn1", co)
+        bn(p + ".bn2", co)
+        cin = co
+    spec["spec_encoder.fc1.weight"] = (cfg["fc_dim"], cin)
+    spec["spec_encoder.fc1.bias"] = (cfg["fc_dim"],)
+    spec["spec_encoder.final_project.weight"] = (cfg["embed_dim"], cfg["fc_dim"])
+    spec["spec_encoder.final_project.bias"] = (cfg["embed_dim"],)
+    spec["logit_scale"] = ()
+    return spec
+
+
+def synthetic_mel(batch, frames=512, n_mels=128, seed=99):
+    """Normalised log-mels as decode_first_stage(z)[:, 0] and wave_to_mel produce them: (B, n_mels, T) in [0, 1].  Smooth random
+    fields (a few low-frequency sinusoids over mel and time plus a little noise), like synthetic_video."""
+    g = torch.Generator().manual_seed(seed)
+    mm, tt = torch.meshgrid(torch.linspace(0, 1, n_mels), torch.arange(frames) / 64.0, indexing="ij")
+    out = torch.zeros(batch, n_mels, frames)
+    for b in range(batch):
+        k = torch.rand(4, 4, generator=g)
+        for j in range(4):
+            fm, ft, ph, am = k[j, 0] * 5, k[j, 1] * 3, k[j, 2] * 6.28, 0.1 + 0.15 * k[j, 3]
+            out[b] += am * torch.sin(6.28 * (fm * mm + ft * tt) + ph)
+    out = out + 0.03 * torch.randn(out.shape, generator=g)
+    return (out + 0.5).clamp_(0, 1)
+
+
 def classifier_spec(cfg=CLS_FULL):
     """Alignment_Classifier_Double_Guidance.state_dict() keys for the backbone (``model.*``)."""
     return unet_spec(cfg, "model.", encoder_only=True)
@@ -268,7 +312,7 @@ def make_tensor(name, shape, seed=0):
     ndim>=2: U(-1,1)*sqrt(3/fan_in)  (unit-gain, also for the reference's zero-initialised
     modules, which would otherwise make the whole network output exactly 0);
     1-D '.weight' (norm scales): 1 + 0.1*U;  1-D '.bias' / running_mean: 0.05*U;  running_var: 1 + 0.2*U;
-    pos_emb: 0.05*U;  CAVP backbone convs: He-uniform U*sqrt(6/fan_in)."""
+    pos_emb: 0.05*U;  CAVP convs and linears of both towers: He-uniform U*sqrt(6/fan_in);  logit_scale: log(1/0.07) + 0.05*U."""
     key = [int(seed) & 0xFFFFFFFFFFFFFFFF, zlib.crc32(name.encode())]
     g = np.random.Generator(np.random.Philox(key=key))
     n = int(np.prod(shape))
@@ -278,10 +322,13 @@ def make_tensor(name, shape, seed=0):
     if len(shape) >= 2:
         if name.endswith("pos_emb.weight"):
             u *= 0.05
-        elif name.startswith("video_encoder."):      # ReLU network: He-uniform; the residual branch's last conv at 1/2
+        elif name.startswith(("video_encoder.", "spec_encoder.")):      # ReLU networks: He-uniform; the residual branch's last conv at 1/2
             u *= np.float32(np.sqrt(6.0 / float(np.prod(shape[1:]))) * (0.5 if ".conv3." in name else 1.0))
         else:
             u *= np.float32(np.sqrt(3.0 / float(np.prod(shape[1:]))))
+    elif name == "logit_scale":                  # around the reference's initial value log(1 / 0.07) (cavp_model.py:43)
+        u *= 0.05
+        u += np.float32(np.log(1 / 0.07))
     elif name.endswith("running_var"):
         u *= 0.2
         u += 1.0

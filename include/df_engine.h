@@ -67,6 +67,16 @@ typedef struct {
   int embed_dim;
 } df_cavp_config;
 
+/* CAVP spectrogram encoder = Cnn14 + final_project (inference/model/cavp_model.py:36, inference/model/cavp_modules.py:1487-1546).
+ * The reference fixes n_mels 128 (the input BatchNorm2d), channels 64 .. 2048 doubling, fc_dim 2048 (fc1 is applied twice, so
+ * fc_dim == channels[5]) and embed_dim 512; carrying them lets a narrow net run the same plan, as stage_blocks does above. */
+typedef struct {
+  int n_mels;
+  int channels[6];
+  int fc_dim;
+  int embed_dim;
+} df_cavp_spec_config;
+
 /* ---- lifetime ------------------------------------------------------------------------------ */
 int df_create(int device, df_ctx** out);
 void df_destroy(df_ctx* ctx);
@@ -116,6 +126,24 @@ int df_cavp_encode(df_ctx* ctx, const float* video_dev, float* out_dev, int B, i
  * projected features, then the optional F.normalize): feat [B][T][C] fp32 (df_cavp_encode with normalize = 0) -> out
  * [B][T / kernel][C], rows L2-normalised when normalize != 0. */
 int df_cavp_pool(const float* feat_dev, float* out_dev, int B, int T, int C, int kernel, int normalize, void* stream);
+
+/* ---- CAVP_Inference.encode_spec(spec, normalize, pool=False) (inference/model/cavp_model.py:68-84 -> Cnn14.forward,
+ * inference/model/cavp_modules.py:1516-1546).  Tensors are loaded under "cavp." + the CAVP_Inference state_dict key
+ * ("cavp.spec_encoder.bn.weight", "cavp.spec_encoder.conv_block3.conv2.weight", "cavp.spec_encoder.fc1.bias", ...); the plan is
+ * built from them at the first call, so a context without them fails there.  spec [B][n_mels][T] fp32, the normalised log-mel as the
+ * caller holds it (the reference's unsqueeze + permute is an address rule of the first kernel) -> out [B][T'][embed_dim] fp32, T' = T
+ * floor-halved four times, rows L2-normalised when normalize != 0.  n_mels must be the configured one and T >= 16 (one output row).
+ * A clip's rows do not depend on its batch-mates: every GEMM's tile and split-K is chosen for the per-sample problem and no tune-table
+ * entry is taken.  Any B >= 1: large batches run as slices inside this call.  The pooled form is df_cavp_pool on the result. */
+int df_config_cavp_spec(df_ctx* ctx, const df_cavp_spec_config* cfg);
+int df_cavp_spec_encode(df_ctx* ctx, const float* spec_dev, float* out_dev, int B, int n_mels, int T, int normalize, void* stream);
+
+/* Audio / video agreement of CAVP features (no reference counterpart: the reference forms the contrastive logits in its training
+ * loss only; this is the frame-wise form of that product for ranking generated candidates against one video).
+ * out[i][j] = scale * mean_t <v[i][t][:], s[j][t][:]>: v [Bv][T][D], s [Bs][T][D], out [Bv][Bs], all fp32, D a multiple of 4.
+ * scale: logit_scale.exp() or 1.  Stateless, no atomics: the result is a pure function of the inputs. */
+int df_cavp_similarity(const float* v_dev, const float* s_dev, float* out_dev, int Bv, int Bs, int T, int D, float scale,
+                       void* stream);
 
 /* ---- UNetModel.forward (openai_unetmodel.py:710-742) through LatentDiffusion.apply_model (ddpm.py:925-1026).
  * The cross-attention context is step-invariant, so it is set once per sample() call: everything of the 16
@@ -459,6 +487,18 @@ int df_test_pack_conv3d_bn(const float* w_dev, const float* gamma_dev, const flo
                            float eps, uint16_t* out_dev, float* bias_dev, int O, int I, int KT, int KH, int KW, int KP, void* stream);
 int df_test_maxpool_time(const float* x_dev, float* out_dev, int B, int T, int C, int k, void* stream);
 int df_test_l2norm_rows(float* x_dev, int rows, int C, void* stream);
+/* The spectrogram tower's own kernels one at a time (csrc/cavp_spec.hip; csrc/kernels.h documents the layouts).  bn0 / bn1: four
+ * device pointers each, {weight, bias, running_mean, running_var}, passed as host arrays of pointers. */
+int df_test_spec_conv_in(const float* spec_dev, const float* const* bn0, const float* w_dev, const float* const* bn1, float eps,
+                         uint16_t* out_dev, int ldo, int B, int n_mels, int T, int C1, void* stream);
+int df_test_avgpool_nhwc(const float* x_dev, int ldx, uint16_t* out_dev, int ldo, int B, int H, int W, int C, int ph, int pw,
+                         void* stream);
+int df_test_spec_head_pool(const float* x_dev, int ldx, uint16_t* out_dev, int ldo, int B, int T, int W, int C, void* stream);
+/* df_cavp_spec_encode of B clips (one slice) with ONE ConvBlock's output copied out as the plan holds it (tests: the hooked stages of
+ * Cnn14.forward): tap 1 .. 5 = conv_block<tap> behind its pool, operand type NHWC [B][h][w][C]; tap 6 = conv_block6, fp32 NHWC (its
+ * (1, 1) pool is the identity).  A plan of its own per tap. */
+int df_test_cavp_spec_tap(df_ctx* ctx, const float* spec_dev, float* out_dev, void* tap_out_dev, int tap, int B, int n_mels, int T,
+                          int normalize, void* stream);
 /* One GEMM with any GemmParams epilogue (csrc/gemm.h) switched on, on a caller-chosen (tile, split-K, batch, gm): the tests of the
  * autotuner's search space.  `size` must be sizeof(df_test_gemm_desc).  Geometry: conv == 0 linear, A [M][lda] (lda 0 = K);
  * conv == 1 a pad-1 3x3 conv, A NHWC [NB][H][Wd][Cin], W [N][9][Cin], M = NB * OH * OW.  Null / zero fields are off.  ldc 0 = N.
