@@ -7,11 +7,27 @@ this package is the Python host side mirroring the reference's interface.
 from . import synth  # noqa: F401
 from . import schedule  # noqa: F401
 from . import engine  # noqa: F401
-from .ldm import (LatentDiffusion, AlignmentClassifier, CAVPInference, DiagonalGaussianDistribution,  # noqa: F401
-                  instantiate_from_config)
+from .ldm import (LatentDiffusion, AlignmentClassifier, AlignmentClassifierMetric, CAVPInference,  # noqa: F401
+                  DiagonalGaussianDistribution, instantiate_from_config)
 from .samplers import DDIMSampler, PLMSSampler, DPMSolverSampler  # noqa: F401
 from .video import ExtractCAVPFeatures, frames_to_tensor  # noqa: F401
 from .vocoder import get_spectrogram, inverse_op, mel_to_wave, wave_to_mel  # noqa: F401
+
+
+def align_metric_config(cls=None, vae=None, cond=None):
+    """``params`` of evaluation/config/eval_classifier.yaml as a plain dict (optionally with shrunken sub-configs)."""
+    cls = dict(synth.CLS_FULL if cls is None else cls)
+    vae = dict(synth.VAE_FULL if vae is None else vae)
+    cond = dict(synth.COND_METRIC if cond is None else cond)
+    return dict(
+        linear_start=0.00085, linear_end=0.0120, timesteps=1000, scale_factor=0.18215, first_stage_key="spec",
+        monitor="val/bce_loss",
+        first_stage_config=stage2_config(vae=vae)["first_stage_config"],
+        classifier_config=dict(target="diff_foley.modules.double_guidance.alignment_backbone.Classifier_Backbone",
+                               params=dict(image_size=32, use_spatial_transformer=True, transformer_depth=1,
+                                           use_checkpoint=True, legacy=False, **cls)),
+        cond_stage_config=dict(target="diff_foley.modules.cond_stage.video_feat_encoder.Video_Feat_Encoder_Posembed",
+                               params=cond))
 
 
 def stage2_config(unet=None, vae=None, cond=None):

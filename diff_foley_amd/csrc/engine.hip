@@ -104,11 +104,23 @@ void df_destroy(df_ctx* ctx) {
 }
 
 int df_config_unet(df_ctx* c, const df_unet_config* cfg) { return guard([&] { c->ucfg = *cfg; c->has_unet = true; }); }
-int df_config_vae(df_ctx* c, const df_vae_config* cfg) { return guard([&] { c->vcfg = *cfg; c->has_vae = true; }); }
+int df_config_vae(df_ctx* c, const df_vae_config* cfg) { return guard([&] { c->vcfg = *cfg; c->has_vae = c->has_vae_shape = true; }); }
 int df_config_vae_encoder(df_ctx* c, const df_vae_encoder_config* cfg) {
   return guard([&] {
     c->has_vae_enc = cfg != nullptr;
     c->ecfg = cfg ? *cfg : df_vae_encoder_config{};
+  });
+}
+// A context that encodes and never decodes (the Align-Acc metric model): the encoder's shape comes with the call, the decoder stays
+// unconfigured -- df_vae_decode refuses, df_prepack packs no decoder, and no decoder tensor is asked for.
+int df_config_vae_encoder_only(df_ctx* c, const df_vae_config* vae, const df_vae_encoder_config* enc) {
+  return guard([&] {
+    if (!vae || !enc) fail("df_config_vae_encoder_only: null configuration");
+    c->vcfg = *vae;
+    c->has_vae = false;
+    c->has_vae_shape = true;
+    c->has_vae_enc = true;
+    c->ecfg = *enc;
   });
 }
 int df_config_cond(df_ctx* c, const df_cond_config* cfg) { return guard([&] { c->kcfg = *cfg; c->has_cond = true; }); }
@@ -148,7 +160,8 @@ int df_finalize(df_ctx* c) {
     if (c->has_unet) build_emb_table(c, 0);
     if (c->has_cls) build_emb_table(c, 1);
     if (c->has_vae_enc) {      // the encoder is configured only by a caller that loads its tensors: every one of them has to be there
-      if (!c->has_vae) fail("vae encoder configured without df_config_vae (it shares the decoder's ch / ch_mult / z_channels)");
+      if (!c->has_vae_shape)
+        fail("vae encoder configured without df_config_vae / df_config_vae_encoder_only (it shares the decoder's ch / ch_mult / z_channels)");
       for (auto& n : vae_encoder_tensor_names(c)) (void)c->rt(n);
     }
     HIPCHK(hipDeviceSynchronize());
@@ -446,7 +459,7 @@ static int vae_encode_chunk(df_ctx* c, int H, int W) {
 
 int df_vae_encode(df_ctx* c, const float* x, float* moments, int B, int H, int W, void* stream) {
   return guard([&] {
-    if (!c->has_vae || !c->has_vae_enc) fail("vae encoder not configured (df_config_vae_encoder, with the encoder's tensors loaded)");
+    if (!c->has_vae_shape || !c->has_vae_enc) fail("vae encoder not configured (df_config_vae_encoder, with the encoder's tensors loaded)");
     need_positive("vae encode", {{"batch", B}, {"H", H}, {"W", W}});
     const int f = 1 << (c->vcfg.n_mult - 1);
     // torch's padded stride-2 convs floor an odd map; this engine sizes every level as H / 2 and refuses what does not divide
@@ -663,6 +676,13 @@ int df_posterior_sample(const float* moments, const float* noise, float* z, int 
   return guard([&] {
     need_positive("posterior sample", {{"batch", B}, {"channels", zc}, {"H*W", HW}});
     HIPCHK(launch_posterior_sample(moments, noise, z, B, zc, (long)HW, scale, (hipStream_t)stream));
+  });
+}
+int df_align_verdict(const float* prob, const float* labels, float* pred, int64_t* counts, int B, void* stream) {
+  return guard([&] {
+    need_positive("align verdict", {{"batch", B}});
+    if (!prob || !pred || !counts) fail("align verdict: null pointer argument");
+    HIPCHK(launch_align_verdict(prob, labels, pred, (long long*)counts, B, (hipStream_t)stream));
   });
 }
 int df_q_sample_blend(const float* img, const float* x0, const float* noise, const float* mask, float* out, int64_t n, int64_t chw,

@@ -232,6 +232,7 @@ struct __attribute__((visibility("hidden"))) df_ctx {
   std::vector<void*> packed_blocks;
   bool has_unet = false, has_vae = false, has_cond = false, has_cls = false, has_cavp = false, has_vae_enc = false, has_cavp_spec = false,
        finalized = false;
+  bool has_vae_shape = false;       // vcfg is set: by df_config_vae (has_vae: the decoder runs) or by df_config_vae_encoder_only (it does not)
   df_cavp_config pcfg{};
   df_cavp_spec_config scfg{};
   df_unet_config ucfg{}, ccfg{};

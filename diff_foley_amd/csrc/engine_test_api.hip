@@ -579,7 +579,7 @@ int df_test_conv3x3_fewin_gemm(const float* x, const float* W, const float* bias
 
 int df_test_vae_encode_tap(df_ctx* c, const float* x, float* moments, float* tap_out, int tap, int B, int H, int W, void* stream) {
   return guard([&] {
-    if (!c->has_vae || !c->has_vae_enc) fail("vae encoder not configured");
+    if (!c->has_vae_shape || !c->has_vae_enc) fail("vae encoder not configured");
     const int f = 1 << (c->vcfg.n_mult - 1);
     if (B <= 0 || B > 16 || H <= 0 || W <= 0 || H % f || W % f || tap < 0) fail("vae encode tap: bad shape %d x %dx%d / tap %d", B, H, W, tap);
     Plan* p = get_plan(c, keyf("vaeenc_tap%d_%d_%d_%d", tap, B, H, W), [&](Plan* pl) { build_vae_encoder(c, pl, B, H, W, tap); });

@@ -84,6 +84,8 @@ hipError_t launch_conv1x1_rows_nchw(const float* h, int ld, const float* Wq, con
 // DiagonalGaussianDistribution.sample() * scale: z = scale * (mean + exp(0.5 * clamp(logvar, -30, 20)) * noise) with moments
 // [B][2*zc][HW] = (mean | logvar), z / noise [B][zc][HW]; noise == nullptr: z = scale * mean (mode())
 hipError_t launch_posterior_sample(const float* moments, const float* noise, float* z, int B, int zc, long HW, float scale, hipStream_t s);
+// pred[b] = rintf(prob[b]); counts[0] += #(pred == label), counts[1] += B (labels NULL: all 1); one block, no atomics (align.hip)
+hipError_t launch_align_verdict(const float* prob, const float* labels, float* pred, long long* counts, int B, hipStream_t s);
 
 // Row softmax: fp32 scores [rows][T] -> bf16 probabilities [rows][T]  (VAE single-head attention)
 // p rows have ldp >= T elements; columns [T, ldp) are written as zeros (the K padding of the P V GEMM)

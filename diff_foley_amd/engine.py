@@ -116,6 +116,7 @@ _SIGS = {
     "df_config_vae": [C.c_void_p, C.POINTER(VaeConfig)],
     "df_config_cond": [C.c_void_p, C.POINTER(CondConfig)],
     "df_config_vae_encoder": [C.c_void_p, C.POINTER(VaeEncoderConfig)],
+    "df_config_vae_encoder_only": [C.c_void_p, C.POINTER(VaeConfig), C.POINTER(VaeEncoderConfig)],
     "df_config_cavp": [C.c_void_p, C.POINTER(CavpConfig)],
     "df_cavp_encode": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p],
     "df_cavp_pool": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p],
@@ -139,6 +140,7 @@ _SIGS = {
     "df_vae_decode": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p],
     "df_vae_encode": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p],
     "df_posterior_sample": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p],
+    "df_align_verdict": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],
     "df_classifier_forward": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                               C.c_int, C.c_void_p],
     "df_classifier_grad": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
@@ -440,14 +442,25 @@ class Engine:
     def config_classifier(self, cfg):
         _chk(self.L.df_config_classifier(self._h, C.byref(unet_config(cfg))), self.L)
 
-    def config_vae(self, cfg, scale_factor):
+    @staticmethod
+    def _vae_config(cfg, scale_factor):
         v = VaeConfig()
         v.z_channels, v.embed_dim, v.ch = cfg["z_channels"], cfg["embed_dim"], cfg["ch"]
         v.num_res_blocks, v.out_ch = cfg["num_res_blocks"], cfg["out_ch"]
         v.ch_mult = _ilist(C.c_int, 8, cfg["ch_mult"])
         v.n_mult = len(cfg["ch_mult"])
         v.scale_factor = float(scale_factor)
-        _chk(self.L.df_config_vae(self._h, C.byref(v)), self.L)
+        return v
+
+    def config_vae(self, cfg, scale_factor):
+        _chk(self.L.df_config_vae(self._h, C.byref(self._vae_config(cfg, scale_factor))), self.L)
+
+    def config_vae_encoder_only(self, cfg, scale_factor):
+        """The VAE encoder + quant_conv in a context that never decodes (df_config_vae_encoder_only): ``cfg`` is the VAE's dict with
+        ``in_channels``; no decoder tensor is loaded, and vae_decode raises."""
+        e = VaeEncoderConfig(int(cfg["in_channels"]))
+        _chk(self.L.df_config_vae_encoder_only(self._h, C.byref(self._vae_config(cfg, scale_factor)), C.byref(e)), self.L)
+        self.vae_in_channels = int(cfg["in_channels"])
 
     def config_vae_encoder(self, cfg):
         """cfg: dict(in_channels=...) with the encoder's tensors about to be loaded, or None: no encoder (encode raises)."""
@@ -913,6 +926,30 @@ def posterior_sample(moments, noise=None, scale=1.0):
     _chk(lib().df_posterior_sample(_ptr(moments), _ptr(noise) if noise is not None else None, _ptr(z), B, c2 // 2, H * W,
                                    float(scale), _stream()))
     return z
+
+
+def align_verdict(prob, labels, counts, pred=None):
+    """One batch of the Align-Acc count (evaluation/align_acc.py:85-86, df_align_verdict): pred = round-half-even(prob),
+    counts[0] += #(pred == label), counts[1] += B.  prob (B,) or (B, 1) fp32; labels the same count of values or None (all 1);
+    counts an int64 device tensor of two elements that the caller zeroed.  Returns pred, shaped like prob.  No host synchronisation."""
+    prob = _dev_f32(prob, prob.device)
+    B = prob.numel()
+    if prob.ndim > 2 or (prob.ndim == 2 and prob.shape[1] != 1):
+        raise ValueError(f"align_verdict: prob must be (B,) or (B, 1), got shape {tuple(prob.shape)}")
+    if counts.dtype != torch.int64 or counts.numel() != 2 or counts.device != prob.device or not counts.is_contiguous():
+        raise ValueError("align_verdict: counts must be a contiguous int64 tensor of two elements on prob's device")
+    if pred is None:
+        pred = torch.empty_like(prob)
+    elif pred.shape != prob.shape or pred.dtype != torch.float32 or pred.device != prob.device or not pred.is_contiguous():
+        raise ValueError("align_verdict: pred must be a contiguous fp32 tensor of prob's shape on prob's device")
+    if labels is not None:
+        labels = _dev_f32(labels, prob.device).reshape(-1)
+        if labels.numel() != B:
+            raise ValueError(f"align_verdict: {labels.numel()} labels for {B} probabilities")
+    if B == 0:
+        return pred
+    _chk(lib().df_align_verdict(_ptr(prob), _ptr(labels) if labels is not None else None, _ptr(pred), _ptr(counts), B, _stream()))
+    return pred
 
 
 def q_sample_blend(img, x0, noise, mask, sqrt_acp, sqrt_one_minus_acp):

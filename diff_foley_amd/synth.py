@@ -305,6 +305,21 @@ def classifier_spec(cfg=CLS_FULL):
     return unet_spec(cfg, "model.", encoder_only=True)
 
 
+COND_METRIC = dict(origin_dim=512, embed_dim=512, seq_len=40)      # evaluation/config/eval_classifier.yaml:53-58
+COND_METRIC_TINY = dict(origin_dim=64, embed_dim=64, seq_len=40)
+
+
+def align_metric_spec(cls=CLS_FULL, vae=VAE_FULL, cond=COND_METRIC):
+    """Alignment_Classifier_metric.state_dict() keys on the evaluation path (alignment_classifier_metric.py:93-100): the VAE encoder +
+    quant_conv under ``first_stage_model.``, the Classifier_Backbone under ``model.`` and the cond stage under ``cond_model.``.  The
+    module's decoder, post_quant_conv, schedule buffers and scale_factor are not on the path."""
+    spec = OrderedDict()
+    spec.update(vae_encoder_spec(dict(vae, in_channels=vae.get("in_channels", 3)), "first_stage_model."))
+    spec.update(classifier_spec(cls))
+    spec.update(cond_spec(cond, "cond_model."))
+    return spec
+
+
 # ----------------------------------------------------------------------------- values
 def make_tensor(name, shape, seed=0):
     """Deterministic fp32 tensor for (name, shape, seed).

@@ -98,6 +98,11 @@ int df_config_cond(df_ctx* ctx, const df_cond_config* cfg);
  * Configured only by a caller that loads those tensors: df_finalize then requires every one of them.  cfg == NULL takes the encoder
  * out of the configuration again.  in_channels above 4 is refused when a plan is built. */
 int df_config_vae_encoder(df_ctx* ctx, const df_vae_encoder_config* cfg);
+/* The same encoder in a context that never decodes (the Align-Acc metric model, alignment_classifier_metric.py:196-210): `vae` gives
+ * the shape the encoder shares with the decoder (ch, ch_mult, num_res_blocks, z_channels, embed_dim); the decoder itself stays
+ * unconfigured, so no post_quant_conv / decoder tensor is loaded or packed and df_vae_decode refuses.  A later df_config_vae
+ * configures the decoder as usual. */
+int df_config_vae_encoder_only(df_ctx* ctx, const df_vae_config* vae, const df_vae_encoder_config* enc);
 int df_config_classifier(df_ctx* ctx, const df_unet_config* cfg);
 /* Tensors of the CAVP video branch are loaded under "cavp." + the CAVP_Inference state_dict key
  * ("cavp.video_encoder.conv1.conv.weight", "cavp.video_encoder.layer1.0.conv1.bn.running_var",
@@ -189,6 +194,12 @@ int df_vae_encode(df_ctx* ctx, const float* x_dev, float* moments_dev, int B, in
  * noise_dev may be NULL: z = scale * mean (mode(), model.py:71-72).  Stateless, like df_lincomb. */
 int df_posterior_sample(const float* moments_dev, const float* noise_dev, float* z_dev, int B, int zc, int HW, float scale,
                         void* stream);
+
+/* ---- Align-Acc verdict of one batch (evaluation/align_acc.py:85-86): pred[b] = prob[b] rounded half to even (torch.round: 0.5 -> 0,
+ * 1.5 -> 2), counts[0] += #(pred[b] == label[b]), counts[1] += B.  prob / pred [B] fp32, labels [B] fp32 or NULL (all 1, :76),
+ * counts int64[2] on the device, zeroed by the caller before the first batch.  One block, one launch, no atomics: calls on one
+ * stream accumulate in order, and a dataset loop reads the counters once, after its last batch.  Stateless, like df_lincomb. */
+int df_align_verdict(const float* prob_dev, const float* labels_dev, float* pred_dev, int64_t* counts_dev, int B, void* stream);
 
 /* ---- Alignment classifier forward (alignment_classifier.py:269-271 -> alignment_backbone.py:656-686)
  * x [B][C][H][W], t [B], video_feat [B][T][context_dim] (raw CAVP features) -> prob [B][out_channels] */
