@@ -7,6 +7,7 @@ a RuntimeError is raised -- results never come from a torch/CPU path.
 import ctypes as C
 import itertools
 import os
+import types
 
 import torch
 
@@ -324,6 +325,32 @@ def _want_dim(what, got, want):
         raise RuntimeError(f"{what}: last dimension is {got}, the loaded model expects {want}")
 
 
+class Configured:
+    """What the ``config_*`` calls of one engine were given: per family, the integers its forward calls check a tensor against and size
+    their outputs with.  The C ABI takes raw pointers, so no forward call runs without them: asking for a family that was never
+    configured raises and names the call it needs.  Plain Python: no ctypes, no device."""
+    NEEDS = dict(unet="config_unet", cls="config_classifier", vae="config_vae / config_vae_encoder_only",
+                 vae_encoder="config_vae_encoder / config_vae_encoder_only", cond="config_cond", cavp="config_cavp",
+                 cavp_spec="config_cavp_spec")
+
+    def __init__(self):
+        self._of = {}
+
+    def record(self, family, **ints):
+        self._of[family] = types.SimpleNamespace(**{k: tuple(int(i) for i in v) if isinstance(v, (list, tuple)) else int(v)
+                                                    for k, v in ints.items()})
+
+    def drop(self, family):
+        self._of.pop(family, None)
+
+    def of(self, family):
+        """The record of ``family`` (attributes named as recorded), the very object stored: no copy per call."""
+        try:
+            return self._of[family]
+        except KeyError:
+            raise RuntimeError(f"{family} is not configured: call Engine.{self.NEEDS[family]}(...) first") from None
+
+
 class PositionOutOfRange(IndexError, RuntimeError):
     """More frames than the cond stage's positional table has rows.  The reference looks the positions up in an nn.Embedding
     (video_feat_encoder.py:16), which answers an index past the table with an IndexError on the CPU and with a RuntimeError (device-side
@@ -423,6 +450,7 @@ class Engine:
         self._last_stream = {}            # plan family -> the torch stream of its previous call (_on)
         self._cls_feat = None             # (feature tensor, (shape, dtype, version), token) of the last classifier_grad call
         self.autotune_on = False
+        self.configured = Configured()
 
     def close(self):
         if getattr(self, "_h", None):
@@ -438,9 +466,11 @@ class Engine:
     # ---- model definition
     def config_unet(self, cfg):
         _chk(self.L.df_config_unet(self._h, C.byref(unet_config(cfg))), self.L)
+        self.configured.record("unet", in_channels=cfg["in_channels"], out_channels=cfg["out_channels"], context_dim=cfg["context_dim"])
 
     def config_classifier(self, cfg):
         _chk(self.L.df_config_classifier(self._h, C.byref(unet_config(cfg))), self.L)
+        self.configured.record("cls", in_channels=cfg["in_channels"], out_channels=cfg["out_channels"], context_dim=cfg["context_dim"])
 
     @staticmethod
     def _vae_config(cfg, scale_factor):
@@ -452,34 +482,41 @@ class Engine:
         v.scale_factor = float(scale_factor)
         return v
 
+    def _record_vae(self, cfg):
+        self.configured.record("vae", z_channels=cfg["z_channels"], embed_dim=cfg["embed_dim"], out_ch=cfg["out_ch"],
+                               n_mult=len(cfg["ch_mult"]))
+
     def config_vae(self, cfg, scale_factor):
         _chk(self.L.df_config_vae(self._h, C.byref(self._vae_config(cfg, scale_factor))), self.L)
+        self._record_vae(cfg)
 
     def config_vae_encoder_only(self, cfg, scale_factor):
         """The VAE encoder + quant_conv in a context that never decodes (df_config_vae_encoder_only): ``cfg`` is the VAE's dict with
-        ``in_channels``; no decoder tensor is loaded, and vae_decode raises."""
+        ``in_channels``; no decoder tensor is loaded, and df_vae_decode refuses ("vae not configured")."""
         e = VaeEncoderConfig(int(cfg["in_channels"]))
         _chk(self.L.df_config_vae_encoder_only(self._h, C.byref(self._vae_config(cfg, scale_factor)), C.byref(e)), self.L)
-        self.vae_in_channels = int(cfg["in_channels"])
+        self._record_vae(cfg)
+        self.configured.record("vae_encoder", in_channels=cfg["in_channels"])
 
     def config_vae_encoder(self, cfg):
         """cfg: dict(in_channels=...) with the encoder's tensors about to be loaded, or None: no encoder (encode raises)."""
         if cfg is None:
             _chk(self.L.df_config_vae_encoder(self._h, None), self.L)
-            self.vae_in_channels = None
+            self.configured.drop("vae_encoder")
             return
         e = VaeEncoderConfig(int(cfg["in_channels"]))
         _chk(self.L.df_config_vae_encoder(self._h, C.byref(e)), self.L)
-        self.vae_in_channels = int(cfg["in_channels"])
+        self.configured.record("vae_encoder", in_channels=cfg["in_channels"])
 
     def config_cond(self, cfg):
         k = CondConfig(cfg["origin_dim"], cfg["embed_dim"], cfg["seq_len"])
         _chk(self.L.df_config_cond(self._h, C.byref(k)), self.L)
+        self.configured.record("cond", origin_dim=cfg["origin_dim"], embed_dim=cfg["embed_dim"], seq_len=cfg["seq_len"])
 
     def config_cavp(self, cfg):
         k = CavpConfig((C.c_int * 4)(*cfg["stage_blocks"]), cfg["base_channels"], cfg["embed_dim"])
-        self.cavp_embed_dim = cfg["embed_dim"]
         _chk(self.L.df_config_cavp(self._h, C.byref(k)), self.L)
+        self.configured.record("cavp", embed_dim=cfg["embed_dim"])
 
     def cavp_encode(self, video, normalize=True):
         """video (B,T,3,H,W) fp32 RGB in [0,1] -> (B,T,embed) (CAVP_Inference.encode_video, pool=False)."""
@@ -487,7 +524,7 @@ class Engine:
         if video.ndim != 5 or video.shape[2] != 3:
             raise RuntimeError(f"cavp_encode: video must be (B,T,3,H,W), got shape {tuple(video.shape)}")
         B, T, c3, H, W = video.shape
-        out = torch.empty(B, T, self.cavp_embed_dim, device=self.device, dtype=torch.float32)
+        out = torch.empty(B, T, self.configured.of("cavp").embed_dim, device=self.device, dtype=torch.float32)
         if out.numel() == 0:              # no clips / no frames: an empty result, like the reference's Conv3d stack on an empty batch
             return out
         _chk(self.L.df_cavp_encode(self._h, _ptr(video), _ptr(out), B, T, H, W, int(bool(normalize)), self._on("cavp")), self.L)
@@ -518,8 +555,8 @@ class Engine:
         """cfg: dict(n_mels, channels[6], fc_dim, embed_dim) -- synth.CAVP_AUDIO_FULL is the reference's Cnn14."""
         k = CavpSpecConfig(int(cfg["n_mels"]), (C.c_int * 6)(*[int(v) for v in cfg["channels"]]), int(cfg["fc_dim"]),
                            int(cfg["embed_dim"]))
-        self.cavp_spec_cfg = dict(cfg)
         _chk(self.L.df_config_cavp_spec(self._h, C.byref(k)), self.L)
+        self.configured.record("cavp_spec", n_mels=cfg["n_mels"], channels=cfg["channels"], embed_dim=cfg["embed_dim"])
 
     @staticmethod
     def cavp_spec_rows(frames):
@@ -527,15 +564,13 @@ class Engine:
         return int(frames) // 2 // 2 // 2 // 2
 
     def _cavp_spec_input(self, spec):
-        cfg = getattr(self, "cavp_spec_cfg", None)
-        if cfg is None:
-            raise RuntimeError("cavp_spec_encode: the spectrogram encoder is not configured (config_cavp_spec)")
+        cfg = self.configured.of("cavp_spec")
         spec = _dev_f32(spec, self.device)
         if spec.ndim != 3:
             raise RuntimeError(f"encode_spec: spec must be (B, n_mels, T), got shape {tuple(spec.shape)}")
         B, M, T = spec.shape
-        if M != cfg["n_mels"]:
-            raise RuntimeError(f"encode_spec: spec has {M} mel bins, the encoder's input BatchNorm has {cfg['n_mels']}")
+        if M != cfg.n_mels:
+            raise RuntimeError(f"encode_spec: spec has {M} mel bins, the encoder's input BatchNorm has {cfg.n_mels}")
         if self.cavp_spec_rows(T) < 1:
             raise RuntimeError(f"encode_spec: {T} frames give no output row (the four (2, 2) pools need at least 16)")
         return spec
@@ -544,7 +579,7 @@ class Engine:
         """spec (B, n_mels, T) fp32 normalised log-mel -> (B, T // 16, embed) (CAVP_Inference.encode_spec, pool=False)."""
         spec = self._cavp_spec_input(spec)
         B, M, T = spec.shape
-        out = torch.empty(B, self.cavp_spec_rows(T), self.cavp_spec_cfg["embed_dim"], device=self.device, dtype=torch.float32)
+        out = torch.empty(B, self.cavp_spec_rows(T), self.configured.of("cavp_spec").embed_dim, device=self.device, dtype=torch.float32)
         if B == 0:                # no clips: an empty result, like the reference's conv stack on an empty batch
             return out
         _chk(self.L.df_cavp_spec_encode(self._h, _ptr(spec), _ptr(out), B, M, T, int(bool(normalize)), self._on("cavpspec")), self.L)
@@ -554,11 +589,11 @@ class Engine:
         """Tests: (features, one ConvBlock's output as fp32 NCHW (B, C, t, mel)) -- df_test_cavp_spec_tap, tap 1 .. 6."""
         spec = self._cavp_spec_input(spec)
         B, M, T = spec.shape
-        out = torch.empty(B, self.cavp_spec_rows(T), self.cavp_spec_cfg["embed_dim"], device=self.device, dtype=torch.float32)
+        out = torch.empty(B, self.cavp_spec_rows(T), self.configured.of("cavp_spec").embed_dim, device=self.device, dtype=torch.float32)
         h, w = T, M
         for i in range(min(tap, 5)):
             h, w = (h // 2 if i < 4 else h), w // 2
-        ch = self.cavp_spec_cfg["channels"][tap - 1]
+        ch = self.configured.of("cavp_spec").channels[tap - 1]
         stage = torch.empty(B, h, w, ch, device=self.device, dtype=torch.float32 if tap == 6 else self.operand_dtype)
         _chk(self.L.df_test_cavp_spec_tap(self._h, _ptr(spec), _ptr(out), _ptr(stage), int(tap), B, M, T, int(bool(normalize)),
                                           self._on("cavpspec")), self.L)
@@ -641,11 +676,11 @@ class Engine:
     def cond_encode(self, feats):
         feats = _dev_f32(feats, self.device)
         B, T, D = feats.shape
-        _want_dim("get_learned_conditioning: video features", D, getattr(self, "cond_origin_dim", None))
-        seq_len = getattr(self, "cond_seq_len", None)
-        if seq_len is not None and T > int(seq_len):
-            raise PositionOutOfRange(f"get_learned_conditioning: {T} frames, the positional table has {seq_len} rows (index out of range)")
-        out = torch.empty(B, T, self.cond_embed_dim, device=self.device, dtype=torch.float32)
+        cond = self.configured.of("cond")
+        _want_dim("get_learned_conditioning: video features", D, cond.origin_dim)
+        if T > cond.seq_len:
+            raise PositionOutOfRange(f"get_learned_conditioning: {T} frames, the positional table has {cond.seq_len} rows (index out of range)")
+        out = torch.empty(B, T, cond.embed_dim, device=self.device, dtype=torch.float32)
         if out.numel() == 0:      # an empty batch / sequence gives an empty result, like the reference's Linear + pos_emb[:0]
             return out
         _chk(self.L.df_cond_encode(self._h, _ptr(feats), _ptr(out), B, T, self._on("cond")), self.L)
@@ -654,7 +689,7 @@ class Engine:
     def set_context(self, ctx):
         ctx = _dev_f32(ctx, self.device)
         N, T, D = ctx.shape
-        _want_dim("cross-attention context", D, getattr(self, "unet_context_dim", None))
+        _want_dim("cross-attention context", D, self.configured.of("unet").context_dim)
         if N == 0:                # empty batch: nothing to precompute (the forward calls return empty tensors)
             return
         _chk(self.L.df_unet_set_context(self._h, _ptr(ctx), N, T, self._on("unet")), self.L)
@@ -671,10 +706,11 @@ class Engine:
 
     def unet_forward(self, x, t, out=None, ts_index=None):
         x = _dev_f32(x, self.device)
-        _want_nchw("UNet input", x, getattr(self, "unet_in_channels", None))
+        unet = self.configured.of("unet")
+        _want_nchw("UNet input", x, unet.in_channels)
         N, Cc, H, W = x.shape
         if out is None:
-            out = torch.empty(N, self.unet_out_channels, H, W, device=self.device, dtype=torch.float32)
+            out = torch.empty(N, unet.out_channels, H, W, device=self.device, dtype=torch.float32)
         if N == 0:                # an empty batch is an empty result (torch modules accept it; no plan exists for it)
             return out
         if ts_index is not None:
@@ -686,10 +722,11 @@ class Engine:
 
     def unet_forward_cfg(self, x, t, scale, out=None, ts_index=None):
         x = _dev_f32(x, self.device)
-        _want_nchw("UNet input", x, getattr(self, "unet_in_channels", None))
+        unet = self.configured.of("unet")
+        _want_nchw("UNet input", x, unet.in_channels)
         B, Cc, H, W = x.shape
         if out is None:
-            out = torch.empty(B, self.unet_out_channels, H, W, device=self.device, dtype=torch.float32)
+            out = torch.empty(B, unet.out_channels, H, W, device=self.device, dtype=torch.float32)
         if B == 0:
             return out
         if ts_index is not None:
@@ -702,25 +739,32 @@ class Engine:
 
     def vae_decode(self, z):
         z = _dev_f32(z, self.device)
-        _want_nchw("decode_first_stage: latent", z, getattr(self, "vae_z_channels", None))
+        vae = self.configured.of("vae")
+        _want_nchw("decode_first_stage: latent", z, vae.z_channels)
         B, Cc, H, W = z.shape
-        up = 2 ** (self.vae_n_mult - 1)
-        out = torch.empty(B, self.vae_out_ch, H * up, W * up, device=self.device, dtype=torch.float32)
+        up = 2 ** (vae.n_mult - 1)
+        out = torch.empty(B, vae.out_ch, H * up, W * up, device=self.device, dtype=torch.float32)
         if B == 0:
             return out
         _chk(self.L.df_vae_decode(self._h, _ptr(z), _ptr(out), B, H, W, self._on("vae")), self.L)
         return out
 
-    def vae_encode(self, x):
-        """x [B][in_channels][H][W] -> moments [B][2*embed_dim][H/f][W/f] = quant_conv(encoder(x)) (df_vae_encode)."""
+    def _vae_encode_io(self, x):
+        """(the image as checked fp32 NCHW on the device, the empty moments [B][2*embed_dim][H/f][W/f])."""
         x = _dev_f32(x, self.device)
-        _want_nchw("encode_first_stage: image", x, getattr(self, "vae_in_channels", None))
+        vae = self.configured.of("vae")
+        _want_nchw("encode_first_stage: image", x, self.configured.of("vae_encoder").in_channels)
         B, Cc, H, W = x.shape
-        f = 2 ** (self.vae_n_mult - 1)
+        f = 2 ** (vae.n_mult - 1)
         if H <= 0 or W <= 0 or H % f or W % f:
             raise RuntimeError(f"encode_first_stage: image {H}x{W} is not a positive multiple of the encoder's downsampling ({f}) "
                                "(the reference floors such maps; this engine refuses them)")
-        out = torch.empty(B, 2 * self.vae_embed_dim, H // f, W // f, device=self.device, dtype=torch.float32)
+        return x, torch.empty(B, 2 * vae.embed_dim, H // f, W // f, device=self.device, dtype=torch.float32)
+
+    def vae_encode(self, x):
+        """x [B][in_channels][H][W] -> moments [B][2*embed_dim][H/f][W/f] = quant_conv(encoder(x)) (df_vae_encode)."""
+        x, out = self._vae_encode_io(x)
+        B, Cc, H, W = x.shape
         if B == 0:
             return out
         _chk(self.L.df_vae_encode(self._h, _ptr(x), _ptr(out), B, H, W, self._on("vaeenc")), self.L)
@@ -728,25 +772,28 @@ class Engine:
 
     def vae_encode_tap(self, x, tap, tap_hwc):
         """Tests: (moments, one intermediate stage as NCHW) of vae_encode -- df_test_vae_encode_tap; tap_hwc = (h, w, C) of the stage."""
-        x = _dev_f32(x, self.device)
+        x, out = self._vae_encode_io(x)
         B, Cc, H, W = x.shape
-        f = 2 ** (self.vae_n_mult - 1)
-        out = torch.empty(B, 2 * self.vae_embed_dim, H // f, W // f, device=self.device, dtype=torch.float32)
         h, w, ch = tap_hwc
         stage = torch.empty(B, h, w, ch, device=self.device, dtype=torch.float32)
         _chk(self.L.df_test_vae_encode_tap(self._h, _ptr(x), _ptr(out), _ptr(stage), int(tap), B, H, W, self._on("vaeenc")), self.L)
         return out, stage.permute(0, 3, 1, 2).contiguous()
 
-    def classifier_forward(self, x, t, feat):
-        x = _dev_f32(x, self.device)
-        feat = _dev_f32(feat, self.device)
-        _want_nchw("classifier input", x, getattr(self, "cls_in_channels", None))
-        B, Cc, H, W = x.shape
-        t = _timesteps(t, B, self.device)
+    def _cls_inputs(self, x, t, feat):
+        """(x, t, feat, the record) as the classifier plans take them: fp32 on the device, checked against the configured backbone."""
+        x, feat = _dev_f32(x, self.device), _dev_f32(feat, self.device)
+        cls = self.configured.of("cls")
+        _want_nchw("classifier input", x, cls.in_channels)
+        B = x.shape[0]
         if feat.ndim != 3 or feat.shape[0] != B:
             raise RuntimeError(f"classifier video_feat: expected [{B}][frames][dim], got shape {tuple(feat.shape)}")
-        _want_dim("classifier video_feat", feat.shape[2], getattr(self, "cls_context_dim", None))
-        out = torch.empty(B, self.cls_out_channels, device=self.device, dtype=torch.float32)
+        _want_dim("classifier video_feat", feat.shape[2], cls.context_dim)
+        return x, _timesteps(t, B, self.device), feat, cls
+
+    def classifier_forward(self, x, t, feat):
+        x, t, feat, cls = self._cls_inputs(x, t, feat)
+        B, Cc, H, W = x.shape
+        out = torch.empty(B, cls.out_channels, device=self.device, dtype=torch.float32)
         if B == 0:
             return out
         _chk(self.L.df_classifier_forward(self._h, _ptr(x), _ptr(t), _ptr(feat), _ptr(out), B, H, W, feat.shape[1],
@@ -770,15 +817,9 @@ class Engine:
         return self._cls_feat[2]
 
     def classifier_grad(self, x, t, feat, want_prob=False):
-        x = _dev_f32(x, self.device)
         token = 0 if os.environ.get("DF_CLS_FEAT_CACHE", "1") == "0" else self._feat_token(feat)
-        feat = _dev_f32(feat, self.device)
-        _want_nchw("classifier input", x, getattr(self, "cls_in_channels", None))
+        x, t, feat, _ = self._cls_inputs(x, t, feat)
         B, Cc, H, W = x.shape
-        t = _timesteps(t, B, self.device)
-        if feat.ndim != 3 or feat.shape[0] != B:
-            raise RuntimeError(f"classifier video_feat: expected [{B}][frames][dim], got shape {tuple(feat.shape)}")
-        _want_dim("classifier video_feat", feat.shape[2], getattr(self, "cls_context_dim", None))
         grad = torch.empty_like(x)
         prob = torch.empty(B, 1, device=self.device, dtype=torch.float32) if want_prob else None
         if B == 0:

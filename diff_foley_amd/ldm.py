@@ -13,65 +13,22 @@ target at :class:`LatentDiffusion` here keeps the rest of t
 Method names, kwargs, return shapes/dtypes follow ddpm.py:568 (get_learned_conditioning), :739 (decode_first_stage),
 :925 (apply_model), :1252 (sample), :1270-1356 (sample_log*).  All compute runs in libdfengine.so (HIP); a missing
 library or a CPU-only host raises -- there is no fallback path.
+
+Holds LatentDiffusion, its sub-module facades, its encoder's posterior, AlignmentClassifier (it runs on the LatentDiffusion's engine)
+and ``instantiate_from_config``; AlignmentClassifierMetric (align_metric.py) and CAVPInference (cavp.py) stay importable from here.
 """
-import functools
 import importlib
-import os
-import threading
-import warnings
 
 import torch
 
 from . import engine as E
 from . import samplers as S
+from .align_metric import (AlignmentClassifierMetric, _MetricBackboneFacade, _MetricCondFacade,  # noqa: F401
+                           _MetricFirstStageFacade, align_acc_clip_name, align_acc_frames, align_acc_specs)
+from .cavp import CAVPInference
+from .model_base import (_EngineModel, _Facade, _check_shapes, _locked, _params, _unet_params, _vae_params,  # noqa: F401
+                         _UNET_FIXED, _UNET_KEYS, _VAE_FIXED)
 from .schedule import BUFFER_NAMES, register_schedule
-
-_UNET_KEYS = ("in_channels", "out_channels", "model_channels", "attention_resolutions", "num_res_blocks",
-              "channel_mult", "num_heads", "context_dim")
-# UNetModel constructor arguments (openai_unetmodel.py:451-468) whose non-default values select code that is not built
-# here; the value the engine implements is listed, anything else raises instead of producing a different network.
-_UNET_FIXED = dict(dims=2, dropout=0, conv_resample=True, num_classes=None, num_head_channels=-1, num_heads_upsample=-1,
-                   use_scale_shift_norm=False, resblock_updown=False, use_new_attention_order=False,
-                   use_spatial_transformer=True, transformer_depth=1, n_embed=None, legacy=False)
-
-
-_VAE_FIXED = dict(attn_resolutions=[], dropout=0.0, resamp_with_conv=True, give_pre_end=False, tanh_out=False,
-                  use_linear_attn=False, attn_type="vanilla")
-
-
-def _vae_params(first_stage_config):
-    """(the engine's VAE dict, double_z) of an AutoencoderKL ``first_stage_config``."""
-    fs = _params(first_stage_config)
-    dd = dict(fs["ddconfig"])
-    # Decoder constructor arguments (stage1_autoencoder/model.py:557-561) whose non-default values select code that is not built
-    # here (attention inside the up levels, conv-less / tanh / pre-end outputs, linear attention): refused, not ignored
-    for k, v in _VAE_FIXED.items():
-        if k in dd and (list(dd[k]) if isinstance(v, list) else dd[k]) != v and not (k == "dropout" and float(dd[k]) == 0.0):
-            raise NotImplementedError(f"first_stage_config.ddconfig: {k}={dd[k]!r} is not supported by libdfengine "
-                                      f"(built for {k}={v!r})")
-    cfg = dict(z_channels=dd["z_channels"], embed_dim=fs["embed_dim"], ch=dd["ch"],
-               ch_mult=[int(v) for v in dd["ch_mult"]], num_res_blocks=dd["num_res_blocks"],
-               out_ch=dd["out_ch"], in_channels=int(dd.get("in_channels", 3)))
-    return cfg, bool(dd.get("double_z", True))
-
-
-def _unet_params(cfg, what):
-    p = _params(cfg)
-    for k, v in _UNET_FIXED.items():
-        if k in p and p[k] != v and not (k == "dropout" and float(p[k]) == 0.0):
-            raise NotImplementedError(f"{what}: {k}={p[k]!r} is not supported by libdfengine (built for {k}={v!r})")
-    out = {k: p[k] for k in _UNET_KEYS}
-    for k in ("attention_resolutions", "channel_mult"):
-        out[k] = [int(v) for v in out[k]]
-    return out
-
-
-def _params(cfg):
-    """Accept {'target':..., 'params': {...}} (YAML form) or the params dict itself."""
-    if cfg is None:
-        return None
-    cfg = dict(cfg)
-    return dict(cfg["params"]) if "params" in cfg else cfg
 
 
 def instantiate_from_config(config):
@@ -88,52 +45,6 @@ def instantiate_from_config(config):
         return alias[target](**dict(config.get("params", dict())))
     module, cls = target.rsplit(".", 1)
     return getattr(importlib.import_module(module), cls)(**dict(config.get("params", dict())))
-
-
-def _check_shapes(state, spec, what):
-    """torch's load_state_dict raises on a size mismatch even with strict=False; the engine's packers take a tensor's own shape, so a
-    checkpoint of another architecture would load and run as a different network.  ``spec``: name -> shape of the configured modules
-    (synth.*_spec: the reference's key layout)."""
-    bad = [f"size mismatch for {k}: copying a param with shape {tuple(v.shape)} from checkpoint, the shape in current model is "
-           f"{tuple(spec[k])}" for k, v in state.items() if k in spec and tuple(v.shape) != tuple(spec[k])]
-    nonfinite = [k for k, v in state.items() if k in spec and v.is_floating_point() and not bool(torch.isfinite(v).all())]
-    if nonfinite:       # the reference would sample NaN; the fp16-operand build's saturating stores would hide it (DESIGN.md section 4)
-        warnings.warn(f"{what}: {len(nonfinite)} checkpoint tensor(s) hold non-finite values ({nonfinite[0]} ...): the fp32 reference "
-                      f"would produce NaN with them", RuntimeWarning, stacklevel=3)
-    if bad:
-        raise RuntimeError(f"Error(s) in loading state_dict for {what}:\n\t" + "\n\t".join(bad[:8]) +
-                           (f"\n\t... and {len(bad) - 8} more" if len(bad) > 8 else ""))
-
-
-def _locked(fn):
-    """One caller at a time per model: a sample() call is a sequence of engine calls that share the model's context operands,
-    timestep table and plan workspaces.  (A torch module's forward is re-entrant from several host threads; this keeps the facade so.)"""
-    @functools.wraps(fn)
-    def run(self, *a, **kw):
-        with self._lock:
-            return fn(self, *a, **kw)
-    return run
-
-
-class _Facade:
-    """Stands where the reference has a sub-module: the forward entry points code outside the samplers calls
-    (`model.model.diffusion_model(x, t, context=c)`, `model.first_stage_model.decode(z)`, `model.cond_stage_model(feats)`) run
-    on the engine; anything that needs the nn.Module tree itself (parameters, children, weights) raises like before -- the
-    weights live in packed HBM buffers owned by libdfengine.so."""
-    _what = "module"
-
-    def __init__(self, owner):
-        object.__setattr__(self, "_m", owner)
-
-    def __getattr__(self, name):
-        raise AttributeError(f"{self._what}.{name}: module tree is not materialised in diff_foley_amd "
-                             "(weights live in packed HBM buffers owned by libdfengine.so)")
-
-    def eval(self):
-        return self
-
-    def cuda(self, device=None):
-        return self
 
 
 class _UNetFacade(_Facade):
@@ -231,7 +142,14 @@ class _CondStageFacade(_Facade):
         return self._m.get_learned_conditioning(c)
 
 
-class LatentDiffusion:
+class LatentDiffusion(_EngineModel):
+    _probe_texts = ("a probe UNet forward (t = 999 / 1)",
+                    "  No operand type was requested, so this model now runs on the bf16 build (fp32 exponent range, same speed; "
+                    "decoded-mel MAE 4.4e-3 against the fp32 reference instead of 5.8e-4).  LatentDiffusion(..., precision='fp16') keeps "
+                    "the fp16 build.",
+                    "  Samples would be clamped silently.  Fallback: LatentDiffusion(..., precision='bf16') (fp32 exponent range, same "
+                    "speed; decoded-mel MAE 4.4e-3 against the fp32 reference instead of 5.8e-4).")
+
     def __init__(self, first_stage_config=None, cond_stage_config=None, unet_config=None, linear_start=1e-4,
                  linear_end=2e-2, timesteps=1000, beta_schedule="linear", channels=3, image_size=256,
                  scale_factor=1.0, conditioning_key=None, parameterization="eps", log_every_t=100,
@@ -239,12 +157,7 @@ class LatentDiffusion:
         # precision: MFMA operand type of the engine.  None -> env DF_PRECISION -> "fp16", the build that meets the north-star
         # tolerance (mel MAE 5.8e-4); "bf16" (BASELINE configs[1]'s wording, same speed) rounds operands 8x coarser and lands at
         # mel MAE 4.5e-3, outside the tolerance -- selectable, never the default.  Not a reference kwarg.
-        self._lock = threading.RLock()
-        self.precision = precision
-        # precision=None (and no DF_PRECISION): the operand type is the PRODUCT's choice, so it is also the product's job to keep
-        # it safe -- if the range probe behind load_state_dict / .cuda() finds fp16 operands at the saturation point with the loaded
-        # weights, the model moves itself to the bf16 build (fp32 exponent range) and says so.  An explicit precision is obeyed.
-        self._auto_precision = precision is None and "DF_PRECISION" not in os.environ
+        super().__init__(precision)
         if parameterization != "eps":
             raise NotImplementedError("only eps-parameterisation is on the path")
         if conditioning_key not in (None, "crossattn"):
@@ -265,11 +178,7 @@ class LatentDiffusion:
         self._buffers = register_schedule(linear_start, linear_end, timesteps, v_posterior, beta_schedule)
         for k, v in self._buffers.items():
             setattr(self, k, v)
-        self.device = torch.device("cpu")
-        self.engine = None
-        self._state = None
         self._ctx_owner = None
-        self.training = False
         self.first_stage_model = _FirstStageFacade(self)
         self.cond_stage_model = _CondStageFacade(self)
         self.model = _DiffusionWrapperFacade(self)
@@ -310,19 +219,13 @@ class LatentDiffusion:
         eng.finalize()
         self._range_check()
 
-    def _range_check(self):
-        """fp16 range guard.  The default operand type (fp16) clamps at +-65504 where the reference (fp32) has no limit, and the
-        tolerance evidence behind that default comes from procedurally generated weights: a trained checkpoint whose activations
-        leave the range would clamp and still return a plausible sample.  So every (re)load of weights is followed by ONE
-        saturation-counted UNet forward at a high and a low timestep (t = 999 and t = 1, one N(0, 1) latent of the model's
-        latent shape, one N(0, 1) context) -- df_debug_saturations counts, per op, the operand-type values stored AT the
-        saturation point.  Any count > 0 raises a RuntimeWarning that names the ops and the fallback.  DF_RANGE_CHECK=0 skips it.
-        (openai_unetmodel.py:710-742 runs in fp32: nothing to guard there.)"""
-        eng = self.engine
-        if eng is None or eng.precision != "fp16" or os.environ.get("DF_RANGE_CHECK", "1") == "0":
-            return []
-        if not any(k.startswith("model.diffusion_model.") for k in (self._state or {})):
-            return []             # a partial (strict=False) load without UNet weights: nothing to probe yet
+    def _probe_ready(self):       # a partial (strict=False) load without UNet weights: nothing to probe yet
+        return any(k.startswith("model.diffusion_model.") for k in (self._state or {}))
+
+    def _probe(self):
+        """The range guard's pass (model_base._EngineModel): one UNet forward at a high and a low timestep (t = 999 and t = 1, one
+        N(0, 1) latent of the model's latent shape, one N(0, 1) context).  (openai_unetmodel.py:710-742 runs in fp32: nothing to guard
+        there.)"""
         # probe shape = the model's configured latent: (channels, H, W) from image_size (an int or an (H, W) pair; the Stage-2
         # config's 8 s latent is 16 x 64) and the condition stage's sequence length
         isz = self.image_size
@@ -337,47 +240,11 @@ class LatentDiffusion:
         x = torch.randn(2, int(self.unet_cfg["in_channels"]), H, W, generator=g).to(self.device)
         c = torch.randn(2, T, int(self.unet_cfg["context_dim"]), generator=g).to(self.device)
         t = torch.tensor([999.0, 1.0], device=self.device)
-        tune_was = getattr(eng, "autotune_on", False)
-        if tune_was:
-            eng.autotune(False)   # the probe plan must not be tuned: load latency, not a product shape
-        bad = []
-        eng.debug_saturations(True)
         try:
-            eng.set_context(c)
-            eng.unet_forward(x, t)
-            torch.cuda.synchronize(self.device)
-            bad = [(lab, n) for lab, n in eng.debug_saturations_read() if n]
-        except RuntimeError as ex:      # the guard must never turn a loadable checkpoint into a load-time error
-            warnings.warn(f"fp16 range probe skipped: {ex}", RuntimeWarning, stacklevel=3)
+            self.engine.set_context(c)
+            self.engine.unet_forward(x, t)
         finally:
-            eng.debug_saturations(False)
             self._ctx_owner = None
-            eng.finalize()        # drops the probe's plans: a later autotune(True) must meet no ready-made plan of this shape
-            if tune_was:
-                eng.autotune(True)
-        if bad and self._auto_precision:
-            shown = ", ".join(f"{lab}: {n}" for lab, n in bad[:6]) + (" ..." if len(bad) > 6 else "")
-            warnings.warn(
-                f"fp16 operands saturated at +-65504 in {len(bad)} op(s) of a probe UNet forward (t = 999 / 1) with these weights -- "
-                f"{shown}.  No operand type was requested, so this model now runs on the bf16 build (fp32 exponent range, same "
-                f"speed; decoded-mel MAE 4.4e-3 against the fp32 reference instead of 5.8e-4).  LatentDiffusion(..., precision='fp16') "
-                f"keeps the fp16 build.", RuntimeWarning, stacklevel=3)
-            self.precision = "bf16"
-            self._auto_precision = False
-            old = self.engine
-            self.engine = E.Engine(self.device, precision="bf16")
-            if getattr(old, "autotune_on", False):
-                self.engine.autotune(True)
-            old.close()
-            self._upload()                # (the bf16 build has no range to probe: _range_check returns at once)
-            return bad
-        if bad:
-            shown = ", ".join(f"{lab}: {n}" for lab, n in bad[:6]) + (" ..." if len(bad) > 6 else "")
-            warnings.warn(
-                f"fp16 operands saturated at +-65504 in {len(bad)} op(s) of a probe UNet forward (t = 999 / 1) with these weights -- "
-                f"{shown}.  Samples would be clamped silently.  Fallback: LatentDiffusion(..., precision='bf16') (fp32 exponent "
-                f"range, same speed; decoded-mel MAE 4.4e-3 against the fp32 reference instead of 5.8e-4).", RuntimeWarning, stacklevel=3)
-        return bad
 
     def _configure(self):
         eng = self.engine
@@ -385,16 +252,6 @@ class LatentDiffusion:
         eng.config_vae(self.vae_cfg, self.scale_factor)
         eng.config_cond(self.cond_cfg)
         eng.config_vae_encoder(dict(in_channels=self.vae_cfg["in_channels"]) if self._has_encoder else None)
-        eng.vae_embed_dim = self.vae_cfg["embed_dim"]
-        eng.cond_embed_dim = self.cond_cfg["embed_dim"]
-        eng.cond_origin_dim = self.cond_cfg["origin_dim"]
-        eng.cond_seq_len = self.cond_cfg["seq_len"]
-        eng.unet_context_dim = self.unet_cfg["context_dim"]
-        eng.unet_out_channels = self.unet_cfg["out_channels"]
-        eng.unet_in_channels = self.unet_cfg["in_channels"]
-        eng.vae_z_channels = self.vae_cfg["z_channels"]
-        eng.vae_out_ch = self.vae_cfg["out_ch"]
-        eng.vae_n_mult = len(self.vae_cfg["ch_mult"])
         return eng
 
     # ---- multi-GPU weight distribution: the root rank packs once, the others import the packed operands ----------
@@ -414,36 +271,6 @@ class LatentDiffusion:
         self.engine.finalize()
         self._state = {}      # (no range probe here: the exporting rank ran it on these very weights)
         return self
-
-    def to(self, device):
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError("diff_foley_amd.LatentDiffusion runs on a ROCm GPU only (no CPU path)")
-        if device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        torch.cuda.set_device(device)
-        self.device = device
-        self.engine = E.Engine(device, precision=self.precision)
-        for k in BUFFER_NAMES:
-            setattr(self, k, getattr(self, k).to(device))
-        if self._state is not None:
-            self._upload()
-        return self
-
-    def cuda(self, device=None):
-        return self.to("cuda" if device is None else device)
-
-    def eval(self):
-        return self
-
-    def autotune(self, enable=True):
-        self._require().autotune(enable)
-        return self
-
-    def _require(self):
-        if self.engine is None or self._state is None:
-            raise RuntimeError("call load_state_dict(...) and .cuda() first")
-        return self.engine
 
     def _cond_tensor(self, cond):
         if isinstance(cond, dict):
@@ -598,9 +425,6 @@ class AlignmentClassifier:
         with ldm._lock:                       # (re)loading tensors finalises the engine: not under another thread's sample()
             self.engine = ldm._require()
             self.engine.config_classifier(self.cfg)
-            self.engine.cls_out_channels = self.cfg["out_channels"]
-            self.engine.cls_in_channels = self.cfg["in_channels"]
-            self.engine.cls_context_dim = self.cfg["context_dim"]
             for k, v in self._state.items():
                 self.engine.load_tensor("classifier." + k, v)
             self.engine.finalize()
@@ -631,499 +455,3 @@ class AlignmentClassifier:
         if self.engine is None:
             raise RuntimeError("AlignmentClassifier.attach(ldm) first")
         return self.engine.classifier_grad(x, t, video_feat)
-
-
-def align_acc_clip_name(file_name):
-    """The clip a generated mel file belongs to: its name with the last two ``_`` fields dropped (evaluation/dataset.py:36), the stem
-    of the clip's ``<name>.npz`` feature file (:91)."""
-    return "_".join(file_name.split("_")[:-2])
-
-
-def align_acc_frames(fps=4, truncate=131072, sr=16000):
-    """Feature rows the evaluation keeps, [0, int(fps * truncate / sr)) (evaluation/dataset.py:95-96): 32 with eval_classifier.yaml."""
-    return int(fps * truncate / sr)
-
-
-def align_acc_specs(specs, channels=3, columns=512):
-    """The metric's input images from either layout: (N, channels, H, W) as the reference's dataset yields them pass through;
-    one-channel mels (N, n_mels, T), as ``decode_first_stage(z)[:, 0]`` and ``wave_to_mel`` give them, are cut to the first ``columns``
-    columns and repeated to ``channels`` channels (evaluation/dataset.py:99-107)."""
-    if specs.ndim == 4:
-        return specs
-    if specs.ndim != 3:
-        raise RuntimeError(f"align_acc: specs must be (N, {channels}, H, W) images or (N, n_mels, T) mels, got shape {tuple(specs.shape)}")
-    return specs[:, None, :, :columns].expand(-1, channels, -1, -1)
-
-
-class _MetricBackboneFacade(_Facade):
-    """Classifier_Backbone.forward(x, timesteps=None, context=None) (alignment_backbone.py:656): the sigmoid probability, (B, 1)."""
-    _what = "model"
-
-    def __call__(self, x, timesteps=None, context=None, y=None, **kwargs):
-        if y is not None:
-            raise NotImplementedError("class-conditional backbone (y=) is not on the path")
-        if timesteps is None or context is None:
-            raise TypeError("model(x, timesteps, context): the backbone needs the timesteps and the encoded video features")
-        return self._m._classify(x, timesteps, context)
-
-
-class _MetricCondFacade(_Facade):
-    """Video_Feat_Encoder_Posembed.forward(x) (video_feat_encoder.py:12-18)."""
-    _what = "cond_model"
-
-    def __call__(self, x):
-        return self._m.encode_cond(x)
-
-
-class _MetricFirstStageFacade(_Facade):
-    """AutoencoderKL.encode(x); the metric model holds no decoder."""
-    _what = "first_stage_model"
-
-    def encode(self, x):
-        return self._m.encode_first_stage(x)
-
-    def decode(self, z):
-        raise NotImplementedError("AlignmentClassifierMetric holds the VAE encoder only: the evaluation never decodes")
-
-
-class AlignmentClassifierMetric:
-    """Mirror of the reference ``Alignment_Classifier_metric`` (alignment_classifier_metric.py:71-288), the model of the Align-Acc
-    metric (evaluation/align_acc.py with evaluation/config/eval_classifier.yaml): VAE encoder + quant_conv, cond stage and
-    Classifier_Backbone under the checkpoint's prefixes ``first_stage_model.``, ``cond_model.`` and ``model.``, in an engine context of
-    its own (as CAVPInference has).  ``model_inference`` (align_acc.py:67-87) runs on it as written:
-
-        z = model.encode_spec_z(spec); c = model.cond_model(video_feat); p = model.model(z, context=c, timesteps=t)
-
-    ``probabilities`` is that chain without a host round trip, ``align_acc`` the dataset loop around it.  The training-side members
-    (q_sample, training_step, optimisers) are not part of this class.  All compute runs in libdfengine.so; there is no fallback."""
-
-    def __init__(self, classifier_config, first_stage_config, cond_stage_config, monitor, first_stage_ckpt=None,
-                 first_stage_key="spec", scale_factor=1.0, timesteps=2, given_betas=None, beta_schedule="linear",
-                 linear_start=1e-4, linear_end=2e-2, cosine_s=8e-3, v_posterior=0., parameterization="eps", *args, **kwargs):
-        self._lock = threading.RLock()
-        # precision: not a reference argument; same meaning and the same automatic fp16 -> bf16 move as LatentDiffusion's
-        self.precision = kwargs.pop("precision", None)
-        self._auto_precision = self.precision is None and "DF_PRECISION" not in os.environ
-        if parameterization not in ("eps", "x0"):
-            raise NotImplementedError("mu not supported")
-        if given_betas is not None:
-            raise NotImplementedError("given_betas is not supported (the schedule is built from linear_start / linear_end)")
-        self.cls_cfg = _unet_params(classifier_config, "classifier_config")
-        self.vae_cfg, double_z = _vae_params(first_stage_config)
-        if not double_z:
-            raise NotImplementedError("first_stage_config.ddconfig: double_z=False is not supported by libdfengine (the posterior "
-                                      "needs mean and logvar)")
-        if not 1 <= self.vae_cfg["in_channels"] <= 4:
-            raise NotImplementedError(f"first_stage_config.ddconfig: in_channels={self.vae_cfg['in_channels']} is not supported by "
-                                      "libdfengine (the encoder's conv_in is built for 1 .. 4 image channels)")
-        self.cond_cfg = {k: int(_params(cond_stage_config)[k]) for k in ("origin_dim", "embed_dim", "seq_len")}
-        if self.cond_cfg["embed_dim"] != self.cls_cfg["context_dim"]:
-            raise ValueError(f"cond_stage_config.embed_dim={self.cond_cfg['embed_dim']} does not match classifier_config.context_dim="
-                             f"{self.cls_cfg['context_dim']}")
-        if self.vae_cfg["embed_dim"] != self.cls_cfg["in_channels"]:
-            raise ValueError(f"first_stage_config.embed_dim={self.vae_cfg['embed_dim']} does not match classifier_config.in_channels="
-                             f"{self.cls_cfg['in_channels']}")
-        self.first_stage_key = first_stage_key
-        self.monitor = monitor
-        self.scale_factor = float(scale_factor)
-        self.v_posterior = v_posterior
-        self.parameterization = parameterization
-        self.num_timesteps = int(timesteps)
-        self.linear_start, self.linear_end = linear_start, linear_end
-        self._buffers = register_schedule(linear_start, linear_end, timesteps, v_posterior, beta_schedule)
-        for k, v in self._buffers.items():
-            setattr(self, k, v)
-        self.device = torch.device("cpu")
-        self.engine = None
-        self._state = None
-        self.training = False
-        self.first_stage_model = _MetricFirstStageFacade(self)
-        self.cond_model = _MetricCondFacade(self)
-        self.model = _MetricBackboneFacade(self)
-        self._first_stage_state = {}
-        self.first_stage_ckpt = first_stage_ckpt
-        if first_stage_ckpt is not None:
-            self.init_first_from_ckpt(first_stage_ckpt)
-
-    # ------------------------------------------------------------------ nn.Module-like plumbing
-    def _spec(self):
-        from . import synth
-        return synth.align_metric_spec(self.cls_cfg, self.vae_cfg, self.cond_cfg)
-
-    def init_first_from_ckpt(self, path):
-        """alignment_classifier_metric.py:179-193: torch.load, ``state_dict`` unwrapped, ``module.`` stripped; the encoder's and
-        quant_conv's tensors are kept for the next upload."""
-        model = torch.load(path, map_location="cpu")
-        if "state_dict" in list(model.keys()):
-            model = model["state_dict"]
-        want = self._spec()
-        new = {"first_stage_model." + k.replace("module.", ""): v for k, v in model.items()}
-        self._first_stage_state = {k: v for k, v in new.items() if k in want}
-        _check_shapes(self._first_stage_state, want, "AlignmentClassifierMetric")
-        missing = [k for k in want if k.startswith("first_stage_model.") and k not in self._first_stage_state]
-        print(f"Restored from {path} with {len(missing)} missing and {len(new) - len(self._first_stage_state)} unexpected keys")
-
-    def load_state_dict(self, state_dict, strict=False):
-        """Takes ``first_stage_model.encoder.*``, ``first_stage_model.quant_conv.*``, ``model.*`` and ``cond_model.*``; the decoder's
-        tensors, when the checkpoint has them, are not kept and not uploaded.  Every tensor of the three modules must be there (here
-        or from ``first_stage_ckpt``): the missing ones are named."""
-        want = self._spec()
-        state = dict(self._first_stage_state)
-        state.update({k: v for k, v in state_dict.items() if k in want})
-        _check_shapes(state, want, "AlignmentClassifierMetric")
-        missing = [k for k in want if k not in state]
-        if missing:
-            raise RuntimeError(f"Error(s) in loading state_dict for AlignmentClassifierMetric:\n\tMissing key(s) in state_dict: "
-                               + ", ".join(missing[:8]) + (f" ... and {len(missing) - 8} more" if len(missing) > 8 else ""))
-        self._state = state
-        if "scale_factor" in state_dict:          # a registered buffer of the reference module: the checkpoint's value wins
-            self.scale_factor = float(state_dict["scale_factor"])
-        for k in BUFFER_NAMES:
-            if k in state_dict:
-                setattr(self, k, state_dict[k].detach().float().to(self.device))
-        unexpected = [k for k in state_dict if k not in want and k not in BUFFER_NAMES and k != "scale_factor"]
-        if strict and unexpected:
-            raise RuntimeError(f"unexpected keys: {unexpected[:5]} ...")
-        if self.engine is not None:
-            self._upload()
-        return [], unexpected
-
-    def _upload(self):
-        eng = self.engine
-        eng.config_vae_encoder_only(self.vae_cfg, self.scale_factor)
-        eng.config_cond(self.cond_cfg)
-        eng.config_classifier(self.cls_cfg)
-        eng.vae_embed_dim = self.vae_cfg["embed_dim"]
-        eng.vae_n_mult = len(self.vae_cfg["ch_mult"])
-        eng.cond_embed_dim = self.cond_cfg["embed_dim"]
-        eng.cond_origin_dim = self.cond_cfg["origin_dim"]
-        eng.cond_seq_len = self.cond_cfg["seq_len"]
-        eng.cls_out_channels = self.cls_cfg["out_channels"]
-        eng.cls_in_channels = self.cls_cfg["in_channels"]
-        eng.cls_context_dim = self.cls_cfg["context_dim"]
-        for k, v in self._state.items():           # the engine's names: the cond stage as LatentDiffusion loads it, the classifier
-            if k.startswith("cond_model."):        # under its "classifier." prefix (include/df_engine.h)
-                k = "cond_stage_model." + k[len("cond_model."):]
-            elif k.startswith("model."):
-                k = "classifier." + k
-            eng.load_tensor(k, v)
-        eng.finalize()
-        self._range_check()
-
-    def _range_check(self):
-        """fp16 range guard, as LatentDiffusion's: one saturation-counted pass of the whole chain (a uniform [0, 1] image that gives a
-        16 x 64 latent, N(0, 1) features, t = 0) after every (re)load.  With no operand type requested a saturated op moves the model
-        to the bf16 build and says so; an explicit precision gets the warning only.  DF_RANGE_CHECK=0 skips it."""
-        eng = self.engine
-        if eng is None or eng.precision != "fp16" or os.environ.get("DF_RANGE_CHECK", "1") == "0":
-            return []
-        f = 2 ** (len(self.vae_cfg["ch_mult"]) - 1)
-        g = torch.Generator(device="cpu").manual_seed(999)
-        x = torch.rand(1, self.vae_cfg["in_channels"], 16 * f, 64 * f, generator=g).to(self.device)
-        feats = torch.randn(1, min(32, self.cond_cfg["seq_len"]), self.cond_cfg["origin_dim"], generator=g).to(self.device)
-        noise = torch.randn(1, self.vae_cfg["embed_dim"], 16, 64, generator=g)
-        tune_was = getattr(eng, "autotune_on", False)
-        if tune_was:
-            eng.autotune(False)
-        bad = []
-        eng.debug_saturations(True)
-        try:
-            self._chain(x, feats, noise)
-            torch.cuda.synchronize(self.device)
-            bad = [(lab, n) for lab, n in eng.debug_saturations_read() if n]
-        except RuntimeError as ex:      # the guard must never turn a loadable checkpoint into a load-time error
-            warnings.warn(f"fp16 range probe skipped: {ex}", RuntimeWarning, stacklevel=3)
-        finally:
-            eng.debug_saturations(False)
-            eng.finalize()              # drops the probe's plans
-            if tune_was:
-                eng.autotune(True)
-        if not bad:
-            return bad
-        shown = ", ".join(f"{lab}: {n}" for lab, n in bad[:6]) + (" ..." if len(bad) > 6 else "")
-        head = f"fp16 operands saturated at +-65504 in {len(bad)} op(s) of a probe pass of the Align-Acc chain with these weights -- {shown}."
-        if self._auto_precision:
-            warnings.warn(head + "  No operand type was requested, so this model now runs on the bf16 build (fp32 exponent range, "
-                          "same speed, 8x the operand rounding).  AlignmentClassifierMetric(..., precision='fp16') keeps the fp16 "
-                          "build.", RuntimeWarning, stacklevel=3)
-            self.precision = "bf16"
-            self._auto_precision = False
-            old = self.engine
-            self.engine = E.Engine(self.device, precision="bf16")
-            if tune_was:
-                self.engine.autotune(True)
-            old.close()
-            self._upload()
-            return bad
-        warnings.warn(head + "  Probabilities would come from clamped activations.  Fallback: AlignmentClassifierMetric(..., "
-                      "precision='bf16').", RuntimeWarning, stacklevel=3)
-        return bad
-
-    def to(self, device):
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError("diff_foley_amd.AlignmentClassifierMetric runs on a ROCm GPU only (no CPU path)")
-        if device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        torch.cuda.set_device(device)
-        self.device = device
-        self.engine = E.Engine(device, precision=self.precision)
-        for k in BUFFER_NAMES:
-            setattr(self, k, getattr(self, k).to(device))
-        if self._state is not None:
-            self._upload()
-        return self
-
-    def cuda(self, device=None):
-        return self.to("cuda" if device is None else device)
-
-    def eval(self):
-        return self
-
-    def autotune(self, enable=True):
-        self._require().autotune(enable)
-        return self
-
-    def _require(self):
-        if self.engine is None or self._state is None:
-            raise RuntimeError("AlignmentClassifierMetric: call load_state_dict(...) and .cuda() first (the model runs in "
-                               "libdfengine.so on a ROCm GPU; there is no CPU fallback)")
-        return self.engine
-
-    # ------------------------------------------------------------------ the path
-    def _classify(self, x, timesteps, context):
-        with self._lock, torch.no_grad():
-            return self._require().classifier_forward(x, timesteps, context)
-
-    def _chain(self, spec, video_feat, noise):
-        """moments -> scale_factor * sample -> cond stage -> backbone at t = 0: the existing plans back to back on the current
-        stream, no host synchronisation."""
-        eng = self._require()
-        moments = eng.vae_encode(spec)
-        if noise is None:
-            noise = torch.randn((moments.shape[0], moments.shape[1] // 2) + tuple(moments.shape[2:]), device=self.device)
-        z = E.posterior_sample(moments, noise, float(self.scale_factor))
-        c = eng.cond_encode(video_feat)
-        return eng.classifier_forward(z, torch.zeros(z.shape[0], device=self.device), c)
-
-    @_locked
-    @torch.no_grad()
-    def encode_first_stage(self, x):
-        """first_stage_model.encode(x) (:196-199): the posterior of the image x [B][in_channels][H][W]."""
-        return DiagonalGaussianDistribution(self._require().vae_encode(x))
-
-    @_locked
-    @torch.no_grad()
-    def get_first_stage_encoding(self, encoder_posterior):
-        """scale_factor * posterior.sample() (:201-204), one launch; the noise is drawn as the reference draws it (torch.randn from the
-        CPU default generator), so torch.manual_seed(s) gives the reference's sample."""
-        self._require()
-        return encoder_posterior.sample(scale=float(self.scale_factor))
-
-    @_locked
-    @torch.no_grad()
-    def encode_spec_z(self, x):
-        return self.get_first_stage_encoding(self.encode_first_stage(x))
-
-    @_locked
-    @torch.no_grad()
-    def encode_cond(self, x):
-        return self._require().cond_encode(x)
-
-    @torch.no_grad()
-    def forward(self, spec_noisy, video_feat, t):
-        """The reference hands its three arguments positionally to the backbone's (x, timesteps, context) (:285-287), which puts the
-        video features where the timesteps belong and cannot run; this follows the intent, as AlignmentClassifier.forward does:
-        ``video_feat`` is the backbone's context (the cond stage's output), ``t`` its timesteps."""
-        return self._classify(spec_noisy, t, video_feat)
-
-    __call__ = forward
-
-    @_locked
-    @torch.no_grad()
-    def probabilities(self, spec, video_feat, noise=None):
-        """(B, 1) fp32 device tensor of p(aligned) for images ``spec`` (B, in_channels, H, W) and raw CAVP features ``video_feat``
-        (B, T, origin_dim): model_inference's chain (align_acc.py:81-84) at t = 0 in one pass, without a host synchronisation.
-        ``noise`` (B, embed_dim, H / f, W / f) replays a posterior draw; None draws it on the device (torch.randn, the device's
-        generator)."""
-        return self._chain(spec, video_feat, noise)
-
-    @_locked
-    @torch.no_grad()
-    def align_acc(self, specs, video_feats, labels=None, batch_size=64, noise=None):
-        """The Align-Acc count of a generated set (eval_audio + model_inference, align_acc.py:67-115): (correct, total) as Python ints.
-        ``specs``: (N, in_channels, H, W) images, or (N, n_mels, T) one-channel mels (align_acc_specs cuts and repeats them);
-        ``video_feats`` (N, T, origin_dim); ``labels`` default to ones (:76).  Runs in slices of ``batch_size``, the last one ragged; the
-        two counters stay on the device (df_align_verdict) and only the return value synchronises with the host.  ``noise`` (not in the
-        reference) replays the posterior draws of the whole set, (N, embed_dim, H / f, W / f)."""
-        self._require()
-        specs = align_acc_specs(specs, self.vae_cfg["in_channels"])
-        N = int(specs.shape[0])
-        if int(video_feats.shape[0]) != N:
-            raise RuntimeError(f"align_acc: {N} specs and {int(video_feats.shape[0])} feature sequences")
-        if int(batch_size) < 1:
-            raise ValueError(f"align_acc: batch_size={batch_size}")
-        if labels is not None:
-            labels = E._dev_f32(torch.as_tensor(labels), self.device).reshape(-1)
-            if labels.numel() != N:
-                raise RuntimeError(f"align_acc: {labels.numel()} labels for {N} specs")
-        counts = torch.zeros(2, dtype=torch.int64, device=self.device)
-        for i in range(0, N, int(batch_size)):
-            sl = slice(i, min(i + int(batch_size), N))
-            p = self._chain(specs[sl], video_feats[sl], None if noise is None else noise[sl])
-            E.align_verdict(p, None if labels is None else labels[sl], counts)
-        correct, total = counts.cpu().tolist()
-        return int(correct), int(total)
-
-
-class CAVPInference:
-    """Mirror of the reference ``CAVP_Inference`` (inference/model/cavp_model.py:9-96), both towers in libdfengine.so:
-    ``encode_video`` = SlowOnly-R50 backbone + ``video_project_head`` (df_cavp_encode; what Stage-2 inference uses, Extract_CAVP_Features,
-    inference/demo_util.py:80-170) and ``encode_spec`` = Cnn14 + ``final_project`` (df_cavp_spec_encode), the tower that reads the
-    normalised log-mel ``decode_first_stage(z)[:, 0]`` and ``wave_to_mel`` produce.  The spectrogram tower is kept when the state dict
-    holds its complete key set (synth.cavp_audio_spec); ``alignment_scores`` ranks generated candidates against a video with the two."""
-
-    def __init__(self, video_encode="Slowonly_pool", spec_encode="cnn14_pool", embed_dim=512, video_pretrained=False,
-                 audio_pretrained=False, stage_blocks=(3, 4, 6, 3), spec_channels=(64, 128, 256, 512, 1024, 2048), spec_fc_dim=2048,
-                 spec_n_mels=128, precision=None, **ignored):
-        if video_encode != "Slowonly_pool":
-            raise NotImplementedError("only video_encode='Slowonly_pool' exists in the reference (cavp_model.py:25)")
-        if spec_encode != "cnn14_pool":
-            raise NotImplementedError("only spec_encode='cnn14_pool' exists in the reference (cavp_model.py:35)")
-        if len(spec_channels) != 6:
-            raise ValueError(f"spec_channels: Cnn14 has six ConvBlocks, got {len(spec_channels)} widths")
-        self.cfg = dict(stage_blocks=[int(v) for v in stage_blocks], base_channels=64, embed_dim=int(embed_dim))
-        # the reference builds Cnn14(embed_dim=512) whatever CAVP_Inference's embed_dim is (cavp_model.py:36); the two agree at 512
-        self.spec_cfg = dict(n_mels=int(spec_n_mels), channels=[int(v) for v in spec_channels], fc_dim=int(spec_fc_dim),
-                             embed_dim=int(embed_dim))
-        self.precision = precision
-        self._state = None
-        self._spec_state = None           # the spectrogram tower's tensors, when the state dict held all of them
-        self._spec_missing = []
-        self.logit_scale = None
-        self.engine = None
-        self.device = torch.device("cpu")
-
-    def load_state_dict(self, state_dict, strict=False):
-        keep = ("video_encoder.", "video_project_head.")
-        self._state = {k: v for k, v in state_dict.items() if k.startswith(keep) and "num_batches_tracked" not in k}
-        from . import synth
-        _check_shapes(self._state, synth.cavp_spec(self.cfg), "CAVPInference")
-        # the spectrogram tower is kept when the state dict holds its COMPLETE key set (the rule the VAE encoder follows in
-        # LatentDiffusion.load_state_dict); with any key missing it is dropped, and its keys are reported as unexpected, as before
-        aspec = synth.cavp_audio_spec(self.spec_cfg)
-        self._spec_missing = [k for k in aspec if k not in state_dict]
-        has_spec = not self._spec_missing
-        self._spec_state = None
-        self.logit_scale = None
-        if has_spec:
-            self._spec_state = {k: state_dict[k] for k in aspec if k != "logit_scale"}
-            _check_shapes(self._spec_state, aspec, "CAVPInference")
-            self.logit_scale = state_dict["logit_scale"].detach().to(torch.float32).reshape(()).cpu()
-        missing = [] if self._state else ["video_encoder.*"]
-        unexpected = [k for k in state_dict if not k.startswith(keep) and not (has_spec and k in aspec)
-                      and not (has_spec and k.startswith("spec_encoder.") and k.endswith("num_batches_tracked"))]
-        if self.engine is not None:
-            self._upload()
-        return missing, unexpected
-
-    def _upload(self):
-        self.engine.config_cavp(self.cfg)
-        if self._state is not None:
-            for k, v in self._state.items():
-                self.engine.load_tensor("cavp." + k, v)
-            if self._spec_state is not None:
-                self.engine.config_cavp_spec(self.spec_cfg)
-                for k, v in self._spec_state.items():
-                    self.engine.load_tensor("cavp." + k, v)
-            self.engine.finalize()
-
-    def to(self, device):
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError("diff_foley_amd.CAVPInference runs on a ROCm GPU only (no CPU path)")
-        if device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        torch.cuda.set_device(device)
-        self.device = device
-        self.engine = E.Engine(device, precision=self.precision)
-        self._upload()
-        return self
-
-    def cuda(self, device=None):
-        return self.to("cuda" if device is None else device)
-
-    def eval(self):
-        return self
-
-    def autotune(self, enable=True):
-        self._require().autotune(enable)
-        return self
-
-    def _require(self):
-        if self.engine is None or self._state is None:
-            raise RuntimeError("CAVPInference: call load_state_dict() and .cuda() first (the encoder runs in "
-                               "libdfengine.so on a ROCm GPU; there is no CPU fallback)")
-        return self.engine
-
-    @torch.no_grad()
-    def encode_video(self, video, normalize=False, train=False, pool=True):
-        """video (B,T,3,H,W) -> (B,T,embed_dim) for pool=False (cavp_model.py:47-65; what Stage-2 inference calls,
-        demo_util.py:161); pool=True adds the contrastive head's MaxPool1d(16) over the frames before the optional normalisation
-        (cavp_model.py:58-59): (B, embed_dim) for 16..31 frames."""
-        if pool:
-            return self._require().cavp_encode_pooled(video, normalize=normalize)
-        return self._require().cavp_encode(video, normalize=normalize)
-
-    def _require_spec(self):
-        eng = self._require()
-        if self._spec_state is None:
-            miss = self._spec_missing or ["spec_encoder.*"]
-            raise NotImplementedError(f"CAVPInference: the spectrogram tower was not loaded -- the state dict lacks {len(miss)} of its "
-                                      f"keys ({', '.join(miss[:3])}{' ...' if len(miss) > 3 else ''})")
-        return eng
-
-    @torch.no_grad()
-    def encode_spec(self, spec, normalize: bool = False, pool=True):
-        """spec (B, n_mels, T) normalised log-mel -> (B, T // 16, embed_dim) for pool=False (cavp_model.py:68-84); pool=True adds the
-        contrastive head's MaxPool1d(16) over the rows before the optional normalisation, under encode_video's rule (Engine.cavp_pool):
-        refused below one 16-row window (T < 256), NotImplementedError for normalize=True over more than one window, (B, embed_dim)
-        for one window."""
-        eng = self._require_spec()
-        if not pool:
-            return eng.cavp_spec_encode(spec, normalize=normalize)
-        return eng.cavp_pool(eng.cavp_spec_encode(spec, normalize=False), normalize, "encode_spec", "feature rows")
-
-    @torch.no_grad()
-    def forward(self, video, spec, output_dict=True):
-        """cavp_model.py:87-96: both towers pooled and normalised, and exp(logit_scale)."""
-        self._require_spec()
-        video_features = self.encode_video(video, normalize=True)
-        spec_features = self.encode_spec(spec, normalize=True)
-        scale = self.logit_scale.exp().to(video_features.device)
-        if output_dict:
-            return {"video_features": video_features, "spec_features": spec_features, "logit_scale": scale}
-        return video_features, spec_features, scale
-
-    __call__ = forward
-
-    @torch.no_grad()
-    def alignment_scores(self, video_feat, spec):
-        """(Bv, Bs) agreement of audio candidates with videos: ``video_feat`` (Bv, T', D) frame features (encode_video(normalize=True,
-        pool=False)), ``spec`` either mels (Bs, n_mels, T) -- encoded here with normalize=True, pool=False -- or their features
-        (Bs, T', D).  scores[i, j] = mean over the frames of <video_feat[i, t], spec_feat[j, t]> (df_cavp_similarity, scale 1): with
-        normalised rows, the mean cosine.  ``scores.argmax(1)`` is the best candidate for each video."""
-        eng = self._require()
-        if video_feat.ndim != 3:
-            raise RuntimeError(f"alignment_scores: video_feat must be (Bv, T', D), got shape {tuple(video_feat.shape)}")
-        if spec.ndim != 3:
-            raise RuntimeError(f"alignment_scores: spec must be mels (Bs, n_mels, T) or features (Bs, T', D), got shape {tuple(spec.shape)}")
-        # features have the video features' (T', D); anything else is a mel (a (Bs, 128, 512) mel also has 512 columns, but 128 rows)
-        is_feat = tuple(spec.shape[1:]) == tuple(video_feat.shape[1:])
-        if not is_feat and spec.shape[1] != self.spec_cfg["n_mels"] and spec.shape[2] == video_feat.shape[2]:
-            is_feat = True            # features of another length: the frame-count check below names the mismatch
-        sf = spec if is_feat else self.encode_spec(spec, normalize=True, pool=False)
-        if sf.shape[1] != video_feat.shape[1]:
-            raise RuntimeError(f"alignment_scores: the audio gives {sf.shape[1]} feature rows, the video has {video_feat.shape[1]} frames "
-                               "(a 4 fps video pairs with 64 mel frames per video frame)")
-        return eng.cavp_similarity(video_feat, sf, 1.0)

@@ -109,9 +109,97 @@ def test_full_chain_vs_reference(prec):
     print(f"align metric: largest |p - p_ref| so far {_worst}")
     with pytest.raises(NotImplementedError, match="encoder only"):
         m.first_stage_model.decode(torch.zeros(1, 4, 16, 64).cuda())
-    m.engine.vae_out_ch = 3                     # the binding's own bookkeeping of a decoding context: the engine itself must refuse
     with pytest.raises(RuntimeError, match="vae not configured"):
         m.engine.vae_decode(torch.zeros(1, 4, 16, 64).cuda())
+
+
+# ---------------------------------------------------------------------------------------------------------- the fp16 range guard
+GEGLU_FACTOR = 3.0e4          # the factor tests/test_path_fp16_gpu.py scales LatentDiffusion's GEGLU projection by
+
+
+def _saturating_sd():
+    """The tiny model's weights with the GEGLU projection of the backbone's first SpatialTransformer scaled by GEGLU_FACTOR."""
+    sd = K.state_dict("tiny", bias=g16()["tiny_bias"])
+    key = sorted(k for k in sd if k.startswith("model.") and k.endswith("transformer_blocks.0.ff.net.0.proj.weight"))[0]
+    sd[key] = sd[key] * GEGLU_FACTOR
+    return sd
+
+
+def _new_metric(sd, **kw):
+    import diff_foley_amd as P
+    m = P.AlignmentClassifierMetric(**kw, **P.align_metric_config(*K.CFG["tiny"]))
+    m.load_state_dict(sd)
+    return m
+
+
+def _probe_left_nothing_behind(m):
+    """The saturation counters are off after a probe, and a normal call still runs."""
+    x, feats, noise = K.inputs("tiny", 8)
+    assert m.engine.debug_saturations_read() == []
+    p = m.probabilities(x[:2].cuda(), feats[:2].cuda(), noise=noise[:2].cuda())
+    assert torch.isfinite(p).all()
+    assert m.engine.debug_saturations_read() == []
+    return p
+
+
+def test_fp16_range_guard_of_the_metric_model(monkeypatch):
+    """The guard behind AlignmentClassifierMetric's load_state_dict + .cuda(): one saturation-counted pass of the Align-Acc chain.
+    Procedural weights: silent.  With the GEGLU projection of model.input_blocks.3.1 scaled by 3.0e4 the fp16 build warns, names the ops
+    and the bf16 fallback, and warns again when the same weights are loaded into the live model; the bf16 build has no range to guard
+    and DF_RANGE_CHECK=0 switches the probe off.  The factor was fixed on the commit before the guard was folded into one template:
+    there 3.0e4 flags 2 ops of the probe pass on an MI355X, that block's GEGLU and the projection behind it
+    (cls_1_16_64_32#30:st.ff1: 65802 stores at +-65504, cls_1_16_64_32#31:st.ffproj: 4935)."""
+    import warnings
+    with warnings.catch_warnings():
+        warnings.simplefilter("error", RuntimeWarning)
+        m = _new_metric(K.state_dict("tiny", bias=g16()["tiny_bias"]), precision="fp16").cuda()
+        assert m._range_check() == []
+    _probe_left_nothing_behind(m)
+    sd = _saturating_sd()
+    m = _new_metric(sd, precision="fp16")
+    with pytest.warns(RuntimeWarning, match=r"fp16 operands saturated.*Align-Acc chain.*precision='bf16'") as rec:
+        m.cuda()
+    print(f"metric range guard: {[str(w.message) for w in rec]}")
+    assert m.engine.precision == "fp16"                       # an explicit precision is obeyed: warning only
+    with pytest.warns(RuntimeWarning, match="saturated") as again:     # re-loading weights into a live engine probes again
+        m.load_state_dict(sd)
+    # both load paths name the caller's line, not one inside the package
+    assert [os.path.basename(w.filename) for w in list(rec) + list(again)] == [os.path.basename(__file__)] * 2
+    _probe_left_nothing_behind(m)
+    with warnings.catch_warnings():
+        warnings.simplefilter("error", RuntimeWarning)
+        _new_metric(sd, precision="bf16").cuda()
+        monkeypatch.setenv("DF_RANGE_CHECK", "0")
+        _new_metric(sd, precision="fp16").cuda()
+
+
+def test_unrequested_precision_moves_the_metric_model_to_bf16_when_fp16_saturates(monkeypatch):
+    """No operand type requested: the saturating weights give ONE warning, the model is on the bf16 build afterwards and its
+    probabilities equal the explicit bf16 model's bit for bit.  A model that was tuning when the weights arrived keeps tuning on its
+    new engine (the flag only: no forward runs here, so nothing is tuned)."""
+    import warnings
+    monkeypatch.delenv("DF_PRECISION", raising=False)
+    sd = _saturating_sd()
+    m = _new_metric(sd)
+    with pytest.warns(RuntimeWarning, match="now runs on the bf16 build") as rec:
+        m.cuda()
+    print(f"metric range guard: {[str(w.message) for w in rec]}")
+    assert len([w for w in rec if issubclass(w.category, RuntimeWarning)]) == 1
+    assert m.precision == m.engine.precision == "bf16"
+    p = _probe_left_nothing_behind(m)
+    mb = _new_metric(sd, precision="bf16").cuda()
+    x, feats, noise = K.inputs("tiny", 8)
+    assert torch.equal(p, mb.probabilities(x[:2].cuda(), feats[:2].cuda(), noise=noise[:2].cuda()))
+    with warnings.catch_warnings():
+        warnings.simplefilter("error", RuntimeWarning)
+        mt = _new_metric(K.state_dict("tiny", bias=g16()["tiny_bias"])).cuda()
+    assert mt.engine.precision == "fp16"
+    mt.autotune(True)
+    old = mt.engine
+    with pytest.warns(RuntimeWarning, match="now runs on the bf16 build"):
+        mt.load_state_dict(sd)
+    assert mt.engine is not old and mt.engine.precision == "bf16" and mt.engine.autotune_on is True
+    assert mt.engine.debug_saturations_read() == []
 
 
 # ---------------------------------------------------------------------------------------------------------- df_align_verdict alone
