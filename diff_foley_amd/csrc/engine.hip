@@ -692,6 +692,27 @@ int df_q_sample_blend(const float* img, const float* x0, const float* noise, con
                                  (hipStream_t)stream));
   });
 }
+int df_q_sample(const float* x0, const float* noise, const int64_t* t, const float* A, const float* S, float* out, int B, int64_t n,
+                int T, void* stream) {
+  return guard([&] {
+    need_positive("q_sample", {{"batch", B}, {"table length", T}});
+    if (n < 1) fail("q_sample: %ld elements per sample (at least 1)", (long)n);
+    if (!x0 || !noise || !t || !A || !S || !out) fail("q_sample: null pointer argument");
+    HIPCHK(launch_q_sample(x0, noise, (const long long*)t, A, S, out, B, (long)n, T, (hipStream_t)stream));
+  });
+}
+int df_diffusion_loss(const float* pred, const float* target, const int64_t* t, const float* logvar, const float* lvlb_weights,
+                      float* loss_simple, float* scalars, int B, int64_t n, int T, int loss_type, float l_simple_weight,
+                      float original_elbo_weight, void* stream) {
+  return guard([&] {
+    need_positive("diffusion_loss", {{"batch", B}, {"table length", T}});
+    if (n < 1) fail("diffusion_loss: %ld elements per sample (at least 1)", (long)n);
+    if (loss_type != 0 && loss_type != 1) fail("diffusion_loss: loss_type = %d (0 = l2, 1 = l1)", loss_type);
+    if (!pred || !target || !t || !logvar || !lvlb_weights || !loss_simple || !scalars) fail("diffusion_loss: null pointer argument");
+    HIPCHK(launch_diffusion_loss(pred, target, (const long long*)t, logvar, lvlb_weights, loss_simple, scalars, B, (long)n, T, loss_type,
+                                 l_simple_weight, original_elbo_weight, (hipStream_t)stream));
+  });
+}
 int df_ddim_update(const float* x, const float* e, const float* noise, float* x_prev, float* pred_x0, int64_t n,
                    float a_t, float a_prev, float sigma_t, float sqrt_one_minus_at, void* stream) {
   return guard([&] {

@@ -86,6 +86,15 @@ hipError_t launch_conv1x1_rows_nchw(const float* h, int ld, const float* Wq, con
 hipError_t launch_posterior_sample(const float* moments, const float* noise, float* z, int B, int zc, long HW, float scale, hipStream_t s);
 // pred[b] = rintf(prob[b]); counts[0] += #(pred == label), counts[1] += B (labels NULL: all 1); one block, no atomics (align.hip)
 hipError_t launch_align_verdict(const float* prob, const float* labels, float* pred, long long* counts, int B, hipStream_t s);
+// out[b] = A[t[b]] * x0[b] + S[t[b]] * noise[b] over [B][n] with t int64 [B] on the device; t[b] outside [0, T): out[b] all NaN, no
+// table read (diffusion.hip)
+hipError_t launch_q_sample(const float* x0, const float* noise, const long long* t, const float* A, const float* S, float* out, int B,
+                           long n, int T, hipStream_t s);
+// loss_simple[b] = mean_n (target - pred)^2 | |target - pred| and the five scalars of loss_dict; two launches, fixed summation order,
+// no atomics (diffusion.hip)
+hipError_t launch_diffusion_loss(const float* pred, const float* target, const long long* t, const float* logvar, const float* lvlb,
+                                 float* loss_simple, float* scalars, int B, long n, int T, int loss_type, float l_simple_weight,
+                                 float original_elbo_weight, hipStream_t s);
 
 // Row softmax: fp32 scores [rows][T] -> bf16 probabilities [rows][T]  (VAE single-head attention)
 // p rows have ldp >= T elements; columns [T, ldp) are written as zeros (the K padding of the P V GEMM)

@@ -164,6 +164,8 @@ _SIGS = {
     "df_lincomb": [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_float), C.c_int, C.c_int64, C.c_void_p],
     "df_q_sample_blend": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int,
                           C.c_float, C.c_float, C.c_void_p],
+    "df_q_sample": [C.c_void_p] * 6 + [C.c_int, C.c_int64, C.c_int, C.c_void_p],
+    "df_diffusion_loss": [C.c_void_p] * 7 + [C.c_int, C.c_int64, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p],
     "df_ddim_update": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float,
                        C.c_float, C.c_float, C.c_void_p],
     "df_plan_count": [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
@@ -1006,6 +1008,81 @@ def q_sample_blend(img, x0, noise, mask, sqrt_acp, sqrt_one_minus_acp):
     _chk(lib().df_q_sample_blend(_ptr(img), _ptr(x0), _ptr(noise), _ptr(mask), _ptr(out), img.numel(), Cc * H * W, H * W,
                                  int(mask.shape[1]), float(sqrt_acp), float(sqrt_one_minus_acp), _stream()))
     return out
+
+
+def _timestep_indices(t, B, T, device, what):
+    """t as an int64 device vector of B table indices.  A host tensor or a list is range-checked HERE (IndexError, as indexing the
+    table on the host would raise) and uploaded; a device tensor is passed on unread -- no host synchronisation -- and the kernel
+    answers an index outside [0, T) with NaN instead of an out-of-bounds read."""
+    if not torch.is_tensor(t):
+        t = torch.as_tensor(t)
+    if t.is_floating_point() or t.dtype == torch.bool:
+        raise TypeError(f"{what}: t must hold integer table indices, got dtype {t.dtype}")
+    if tuple(t.shape) != (B,):
+        raise ValueError(f"{what}: t of shape {tuple(t.shape)}, expected ({B},) -- one table index per sample")
+    if t.device.type == "cpu":
+        bad = [int(v) for v in t.tolist() if not 0 <= int(v) < T]
+        if bad:
+            raise IndexError(f"{what}: index {bad[0]} is out of bounds for a table of {T} entries")
+    return t.to(device=device, dtype=torch.int64).contiguous()
+
+
+def _table(tab, device, what):
+    tab = _dev_f32(tab, device)
+    if tab.ndim != 1 or tab.numel() < 1:
+        raise ValueError(f"{what}: a table must be a non-empty vector, got shape {tuple(tab.shape)}")
+    return tab
+
+
+def q_sample(x0, noise, t, sqrt_acp, sqrt_one_minus_acp):
+    """out[b] = sqrt_acp[t[b]] * x0[b] + sqrt_one_minus_acp[t[b]] * noise[b] (ddpm.py:279-282, ddim.py:412-413; df_q_sample).
+    x0 fp32 [B][...] on its device, noise of x0's shape, t (B,) integer indices (device tensor: not read on the host), the two tables
+    fp32 vectors of one length."""
+    dev = x0.device
+    x0 = _dev_f32(x0, dev)
+    if tuple(noise.shape) != tuple(x0.shape):
+        raise ValueError(f"q_sample: noise of shape {tuple(noise.shape)}, expected {tuple(x0.shape)} (the shape of x_start)")
+    noise = _dev_f32(noise, dev)
+    A, S = _table(sqrt_acp, dev, "q_sample"), _table(sqrt_one_minus_acp, dev, "q_sample")
+    if A.numel() != S.numel():
+        raise ValueError(f"q_sample: tables of {A.numel()} and {S.numel()} entries")
+    B = int(x0.shape[0]) if x0.ndim else 0
+    t = _timestep_indices(t, B, A.numel(), dev, "q_sample")
+    out = torch.empty_like(x0)
+    if out.numel() == 0:
+        return out
+    _chk(lib().df_q_sample(_ptr(x0), _ptr(noise), _ptr(t), _ptr(A), _ptr(S), _ptr(out), B, out.numel() // B, A.numel(), _stream()))
+    return out
+
+
+LOSS_TYPES = {"l2": 0, "l1": 1}
+
+
+def diffusion_loss(pred, target, t, logvar, lvlb_weights, loss_type="l2", l_simple_weight=1.0, original_elbo_weight=0.0):
+    """(loss_simple [B], scalars [5]) of df_diffusion_loss, both fp32 on pred's device and not read here: the per-sample mean of
+    (target - pred)^2 | |target - pred| and { mean(loss_simple), mean(loss_simple / exp(logvar[t]) + logvar[t]),
+    mean(lvlb_weights[t] * loss_simple), l_simple_weight * [1] + original_elbo_weight * [2], mean(logvar) } (ddpm.py:1061-1079).
+    An empty batch returns an empty loss_simple and NaN scalars (the mean of nothing), without a launch."""
+    if loss_type not in LOSS_TYPES:
+        raise NotImplementedError(f"unknown loss type '{loss_type}'")
+    dev = pred.device
+    pred = _dev_f32(pred, dev)
+    if tuple(target.shape) != tuple(pred.shape):
+        raise ValueError(f"diffusion_loss: target of shape {tuple(target.shape)}, expected {tuple(pred.shape)} (the shape of pred)")
+    target = _dev_f32(target, dev)
+    lv, w = _table(logvar, dev, "diffusion_loss"), _table(lvlb_weights, dev, "diffusion_loss")
+    if lv.numel() != w.numel():
+        raise ValueError(f"diffusion_loss: tables of {lv.numel()} and {w.numel()} entries")
+    B = int(pred.shape[0]) if pred.ndim else 0
+    t = _timestep_indices(t, B, lv.numel(), dev, "diffusion_loss")
+    loss_simple = torch.empty(B, device=dev, dtype=torch.float32)
+    if pred.numel() == 0:
+        return loss_simple.fill_(float("nan")), torch.full((5,), float("nan"), device=dev, dtype=torch.float32)
+    scalars = torch.empty(5, device=dev, dtype=torch.float32)
+    _chk(lib().df_diffusion_loss(_ptr(pred), _ptr(target), _ptr(t), _ptr(lv), _ptr(w), _ptr(loss_simple), _ptr(scalars), B,
+                                 pred.numel() // B, lv.numel(), LOSS_TYPES[loss_type], float(l_simple_weight),
+                                 float(original_elbo_weight), _stream()))
+    return loss_simple, scalars
 
 
 def ddim_update(x, e, a_t, a_prev, sigma_t, sqrt_one_minus_at, noise=None):

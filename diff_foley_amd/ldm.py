@@ -1,4 +1,4 @@
-"""Drop-in for the reference's ``LatentDiffusion`` on MI355X (sampling API only).
+"""Drop-in for the reference's ``LatentDiffusion`` on MI355X (the sampling API, and the training objective evaluated without a gradient).
 
 ``instantiate_from_config(config.model)`` of the reference notebook (inference/diff_foley_inference.ipynb:80-95,
 diff_foley/util.py:176-191) resolves ``target: diff_foley.models.diffusion.ddpm.LatentDiffusion``; pointing that
@@ -11,8 +11,8 @@ target at :class:`LatentDiffusion` here keeps the rest of t
     mel = model.decode_first_stage(z)[:, 0]
 
 Method names, kwargs, return shapes/dtypes follow ddpm.py:568 (get_learned_conditioning), :739 (decode_first_stage),
-:925 (apply_model), :1252 (sample), :1270-1356 (sample_log*).  All compute runs in libdfengine.so (HIP); a missing
-library or a CPU-only host raises -- there is no fallback path.
+:925 (apply_model), :1252 (sample), :1270-1356 (sample_log*), :279-297 (q_sample, get_loss), :904-913 (forward), :1046-1081
+(p_losses).  All compute runs in libdfengine.so (HIP); a missing library or a CPU-only host raises -- there is no fallback path.
 
 Holds LatentDiffusion, its sub-module facades, its encoder's posterior, AlignmentClassifier (it runs on the LatentDiffusion's engine)
 and ``instantiate_from_config``; AlignmentClassifierMetric (align_metric.py) and CAVPInference (cavp.py) stay importable from here.
@@ -143,6 +143,7 @@ class _CondStageFacade(_Facade):
 
 
 class LatentDiffusion(_EngineModel):
+    _buffer_names = BUFFER_NAMES + ("lvlb_weights", "logvar")      # the loss tables move to the device with the schedule
     _probe_texts = ("a probe UNet forward (t = 999 / 1)",
                     "  No operand type was requested, so this model now runs on the bf16 build (fp32 exponent range, same speed; "
                     "decoded-mel MAE 4.4e-3 against the fp32 reference instead of 5.8e-4).  LatentDiffusion(..., precision='fp16') keeps "
@@ -153,7 +154,8 @@ class LatentDiffusion(_EngineModel):
     def __init__(self, first_stage_config=None, cond_stage_config=None, unet_config=None, linear_start=1e-4,
                  linear_end=2e-2, timesteps=1000, beta_schedule="linear", channels=3, image_size=256,
                  scale_factor=1.0, conditioning_key=None, parameterization="eps", log_every_t=100,
-                 v_posterior=0.0, use_ema=True, clip_denoised=True, precision=None, **ignored):
+                 v_posterior=0.0, use_ema=True, clip_denoised=True, precision=None, loss_type="l2", l_simple_weight=1.0,
+                 original_elbo_weight=0.0, logvar_init=0.0, learn_logvar=False, **ignored):
         # precision: MFMA operand type of the engine.  None -> env DF_PRECISION -> "fp16", the build that meets the north-star
         # tolerance (mel MAE 5.8e-4); "bf16" (BASELINE configs[1]'s wording, same speed) rounds operands 8x coarser and lands at
         # mel MAE 4.5e-3, outside the tolerance -- selectable, never the default.  Not a reference kwarg.
@@ -178,6 +180,14 @@ class LatentDiffusion(_EngineModel):
         self._buffers = register_schedule(linear_start, linear_end, timesteps, v_posterior, beta_schedule)
         for k, v in self._buffers.items():
             setattr(self, k, v)
+        # the training objective's settings (ddpm.py:102-104, 114-119), read by get_loss / p_losses
+        if loss_type not in E.LOSS_TYPES:
+            raise NotImplementedError(f"unknown loss type '{loss_type}'")          # ddpm.py:295 raises at the first get_loss
+        self.loss_type = loss_type
+        self.l_simple_weight = l_simple_weight
+        self.original_elbo_weight = original_elbo_weight
+        self.learn_logvar = bool(learn_logvar)
+        self.logvar = torch.full(fill_value=float(logvar_init), size=(self.num_timesteps,))
         self._ctx_owner = None
         self.first_stage_model = _FirstStageFacade(self)
         self.cond_stage_model = _CondStageFacade(self)
@@ -200,10 +210,12 @@ class LatentDiffusion(_EngineModel):
             self._state.update({k: state_dict[k] for k in enc_spec})
         _check_shapes(self._state, synth.state_dict_spec(self.unet_cfg, self.vae_cfg, self.cond_cfg, with_encoder=self._has_encoder),
                       "LatentDiffusion")
-        for k in BUFFER_NAMES:            # checkpoints carry the schedule buffers too
+        for k in BUFFER_NAMES + ("logvar",):      # checkpoints carry the schedule buffers too, and logvar (learn_logvar: a parameter)
             if k in state_dict:
-                setattr(self, k, state_dict[k].detach().float().cpu())
-        unexpected = [k for k in state_dict if not k.startswith(need) and k not in BUFFER_NAMES
+                if k == "logvar" and tuple(state_dict[k].shape) != (self.num_timesteps,):
+                    raise RuntimeError(f"LatentDiffusion: logvar has shape {tuple(state_dict[k].shape)}, expected ({self.num_timesteps},)")
+                setattr(self, k, state_dict[k].detach().float().to(self.device))
+        unexpected = [k for k in state_dict if not k.startswith(need) and k not in BUFFER_NAMES + ("logvar",)
                       and not (self._has_encoder and k in enc_spec)]
         if strict and unexpected:
             raise RuntimeError(f"unexpected keys: {unexpected[:5]} ...")
@@ -352,6 +364,82 @@ class LatentDiffusion(_EngineModel):
         # q_noise_fn are this package's replay hooks (no reference name) and are obeyed.
         return S.ancestral_sample(self, cond, tuple(shape), x_T=x_T, timesteps=timesteps, return_intermediates=return_intermediates,
                                   noise_fn=kwargs.get("noise_fn"), mask=mask, x0=x0, q_noise_fn=kwargs.get("q_noise_fn"))
+
+    # ------------------------------------------------------------------ the training objective, evaluated (no gradient)
+    @_locked
+    @torch.no_grad()
+    def q_sample(self, x_start, t, noise=None):
+        """ddpm.py:279-282: sqrt_alphas_cumprod[t] * x_start + sqrt_one_minus_alphas_cumprod[t] * noise with one timestep PER SAMPLE
+        (t: (B,) integers; a device tensor is not read on the host) -- one df_q_sample."""
+        self._require()
+        x_start = E._dev_f32(x_start, self.device)
+        if noise is None:
+            noise = torch.randn_like(x_start)
+        return E.q_sample(x_start, noise, t, self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod)
+
+    @_locked
+    @torch.no_grad()
+    def get_loss(self, pred, target, mean=True):
+        """ddpm.py:284-297.  mean=True is df_diffusion_loss's first scalar (equal sample sizes: the mean of the per-sample means is the
+        mean); mean=False -- the element-wise map, which p_losses never materialises -- is a torch expression on the device tensors."""
+        self._require()
+        pred, target = E._dev_f32(pred, self.device), E._dev_f32(target, self.device)
+        if tuple(pred.shape) != tuple(target.shape):
+            raise ValueError(f"get_loss: target of shape {tuple(target.shape)}, expected {tuple(pred.shape)} (the shape of pred)")
+        if not mean:
+            d = target - pred
+            return d.abs() if self.loss_type == "l1" else d * d
+        rows = pred.reshape(pred.shape[0], -1) if pred.ndim > 1 else pred.reshape(1, -1)
+        t0 = torch.zeros(rows.shape[0], dtype=torch.int64, device=self.device)
+        return E.diffusion_loss(rows, target.reshape(rows.shape), t0, self.logvar, self.lvlb_weights, self.loss_type)[1][0]
+
+    @_locked
+    @torch.no_grad()
+    def p_losses(self, x_start, cond, t, noise=None):
+        """ddpm.py:1046-1081 in eval mode: (loss, loss_dict) of the eps-objective at the per-sample timesteps t -- df_q_sample, the
+        UNet through apply_model, df_diffusion_loss.  loss is a 0-dim device tensor; the values of loss_dict ('val/loss_simple',
+        with learn_logvar 'val/loss_gamma' and 'logvar', 'val/loss_vlb', 'val/loss') are Python floats read with ONE device-to-host
+        copy at the end -- nothing else in the call waits for the device."""
+        self._require()
+        x_start = E._dev_f32(x_start, self.device)
+        if x_start.ndim != 4:
+            raise ValueError(f"p_losses: x_start of shape {tuple(x_start.shape)}, expected [B][C][H][W]")
+        B = int(x_start.shape[0])
+        if noise is None:
+            noise = torch.randn_like(x_start)
+        elif tuple(noise.shape) != tuple(x_start.shape):
+            raise ValueError(f"p_losses: noise of shape {tuple(noise.shape)}, expected {tuple(x_start.shape)} (the shape of x_start)")
+        noise = E._dev_f32(noise, self.device)
+        t = E._timestep_indices(t, B, self.num_timesteps, self.device, "p_losses")
+        if x_start.numel() == 0:          # the mean of nothing
+            scalars = torch.full((5,), float("nan"), device=self.device)
+        else:
+            x_noisy = E.q_sample(x_start, noise, t, self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod)
+            model_output = self.apply_model(x_noisy, t, cond)
+            _, scalars = E.diffusion_loss(model_output, noise, t, self.logvar, self.lvlb_weights, self.loss_type,
+                                          self.l_simple_weight, self.original_elbo_weight)
+        simple, gamma, vlb, total, logvar = scalars.tolist()      # the one device-to-host copy
+        prefix = "train" if self.training else "val"
+        loss_dict = {f"{prefix}/loss_simple": simple}
+        if self.learn_logvar:
+            loss_dict[f"{prefix}/loss_gamma"] = gamma
+            loss_dict["logvar"] = logvar
+        loss_dict[f"{prefix}/loss_vlb"] = vlb
+        loss_dict[f"{prefix}/loss"] = total
+        return scalars[3], loss_dict
+
+    @_locked
+    @torch.no_grad()
+    def forward(self, x, c, *args, **kwargs):
+        """ddpm.py:904-913 for the trainable cond stage of Stage2_LDM.yaml: t ~ randint(0, num_timesteps) per sample, drawn on the
+        device, c through get_learned_conditioning, then p_losses.  (shorten_cond_schedule is not on the path.)"""
+        self._require()
+        t = torch.randint(0, self.num_timesteps, (x.shape[0],), device=self.device).long()
+        assert c is not None
+        c = self.get_learned_conditioning(c)
+        return self.p_losses(x, c, t, *args, **kwargs)
+
+    __call__ = forward
 
     def _sampler(self, name):
         return {"DDIM": S.DDIMSampler, "DPM_Solver": S.DPMSolverSampler, "PLMS": S.PLMSSampler}[name](self)

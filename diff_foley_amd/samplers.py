@@ -16,7 +16,7 @@ import warnings
 import torch
 
 from . import engine as E
-from .schedule import DDIMTables, DPMTables
+from .schedule import DDIMTables, DPMTables, original_step_tables
 
 import os as _os
 _NO_HOIST = bool(int(_os.environ.get("DF_NO_THOIST", "0")))      # A/B switch: time embedding inside every step
@@ -194,6 +194,73 @@ class DDIMSampler(object):
         self.ddim_alphas_prev = self.tables.alphas_prev
         self.ddim_sigmas = self.tables.sigmas
         self.ddim_sqrt_one_minus_alphas = self.tables.sqrt_one_minus_alphas
+        # the use_original_steps=True tables (ddim.py:34-40, 53-56, 254-257) belong to this schedule too; sample() never reads them,
+        # so they are built when stochastic_encode / decode first ask (__getattr__), from the eta given here
+        self._original_eta = ddim_eta
+        self._original = None
+        self._encode_tables = {}      # use_original_steps -> the two device tables of stochastic_encode, uploaded on first use
+
+    # attribute of the reference's sampler after make_schedule -> key of schedule.original_step_tables
+    _ORIGINAL = {"alphas_cumprod": "alphas_cumprod", "alphas_cumprod_prev": "alphas_cumprod_prev",
+                 "sqrt_alphas_cumprod": "sqrt_alphas_cumprod", "sqrt_one_minus_alphas_cumprod": "sampler_sqrt_one_minus_alphas_cumprod",
+                 "ddim_sigmas_for_original_num_steps": "ddim_sigmas_for_original_num_steps"}
+
+    def __getattr__(self, name):      # reached only for names that are not set: the original-step tables, built on first use
+        if name != "original" and name not in self._ORIGINAL:
+            raise AttributeError(f"'{type(self).__name__}' object has no attribute '{name}'")
+        d = self.__dict__
+        if "_original_eta" not in d:      # no make_schedule yet: the reference's sampler has no such attribute either
+            raise AttributeError(f"'{type(self).__name__}' object has no attribute '{name}' (call make_schedule first)")
+        if d["_original"] is None:
+            m = self.model
+            d["_original"] = original_step_tables(m.alphas_cumprod, m.alphas_cumprod_prev, m.sqrt_one_minus_alphas_cumprod,
+                                                  d["_original_eta"])
+        return d["_original"] if name == "original" else d["_original"][self._ORIGINAL[name]]
+
+    @torch.no_grad()
+    def stochastic_encode(self, x0, t, use_original_steps=False, noise=None):
+        """ddim.py:400-413: x0 noised to the DDIM step (or, use_original_steps, the DDPM step) whose TABLE INDEX is t[b] -- one
+        df_q_sample.  Fast, but no exact reconstruction (the reference's words).  Needs make_schedule first, like the reference:
+        without it the tables are missing attributes, here as there."""
+        if use_original_steps:
+            tabs = (self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod)
+        else:
+            tabs = (np.sqrt(self.ddim_alphas), self.ddim_sqrt_one_minus_alphas)
+        dev = self.model.device
+        key = bool(use_original_steps)
+        if key not in self._encode_tables:
+            self._encode_tables[key] = tuple(torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)).to(dev) for v in tabs)
+        A, S = self._encode_tables[key]
+        x0 = E._dev_f32(x0, dev)
+        if noise is None:
+            noise = torch.randn_like(x0)
+        return E.q_sample(x0, noise, t, A, S)
+
+    @torch.no_grad()
+    def decode(self, x_latent, cond, t_start, unconditional_guidance_scale=1.0, unconditional_conditioning=None,
+               use_original_steps=False):
+        """ddim.py:415-434: denoise x_latent from table index t_start down to 0 under ``cond`` -- the step loop of sample() over
+        timesteps[:t_start], flipped.  sigma is the table's, so make_schedule's ddim_eta applies; noise_fn (tests) is not a
+        parameter here: set ``self.noise_fn`` to replay a recorded noise sequence."""
+        if use_original_steps:
+            timesteps = np.arange(self.ddpm_num_timesteps)
+            o = self.original
+            tables = (o["alphas_cumprod"], o["alphas_cumprod_prev"], o["ddim_sigmas_for_original_num_steps"],
+                      o["sqrt_one_minus_alphas_cumprod"])
+        else:
+            timesteps = self.ddim_timesteps
+            tables = (self.ddim_alphas, self.ddim_alphas_prev, self.ddim_sigmas, self.ddim_sqrt_one_minus_alphas)
+        timesteps = timesteps[:t_start]
+        total_steps = timesteps.shape[0]
+        print(f"Running DDIM Sampling with {total_steps} timesteps")
+        if total_steps == 0:
+            return x_latent
+        x = E._dev_f32(x_latent, self.model.device)
+        if x.ndim != 4:
+            raise ValueError(f"decode: x_latent of shape {tuple(x.shape)}, expected [B][C][H][W]")
+        x_dec, _ = self._steps(x, tuple(x.shape), np.flip(timesteps), tables, cond, unconditional_guidance_scale,
+                               unconditional_conditioning, noise_fn=getattr(self, "noise_fn", None))
+        return x_dec
 
     @torch.no_grad()
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None,
@@ -211,18 +278,32 @@ class DDIMSampler(object):
         size = (batch_size, C, H, W)
         img = torch.randn(size, device=dev) if x_T is None else x_T.to(dev, torch.float32).contiguous()
         tb = self.tables
-        steps = np.flip(tb.timesteps)
+        return self._steps(img, size, np.flip(tb.timesteps), (tb.alphas, tb.alphas_prev, tb.sigmas, tb.sqrt_one_minus_alphas),
+                           conditioning, unconditional_guidance_scale, unconditional_conditioning, noise_fn=noise_fn,
+                           temperature=temperature, noise_dropout=noise_dropout, score_corrector=score_corrector,
+                           corrector_kwargs=corrector_kwargs, classifier=classifier, origin_cond=origin_cond,
+                           classifier_guide_scale=classifier_guide_scale, callback=callback, img_callback=img_callback,
+                           log_every_t=log_every_t, paint=_Inpaint(self.model, mask, x0, size, kwargs.get("q_noise_fn")))
+
+    def _steps(self, img, size, steps, tables, conditioning, unconditional_guidance_scale, unconditional_conditioning, noise_fn=None,
+               temperature=1.0, noise_dropout=0.0, score_corrector=None, corrector_kwargs=None, classifier=None, origin_cond=None,
+               classifier_guide_scale=0.0, callback=None, img_callback=None, log_every_t=100, paint=None):
+        """The DDIM step loop (ddim.py:179-229 with p_sample_ddim :231-273): ``steps`` are the timestep values in visiting order,
+        ``tables`` = (alphas, alphas_prev, sigmas, sqrt_one_minus_alphas) indexed by len(steps) - 1 - i at step i.  sample() walks the
+        whole DDIM schedule, decode() a prefix of it (or of the original steps): one loop for both."""
+        dev = self.model.device
+        batch_size = size[0]
+        alphas, alphas_prev, sigmas, sqrt_one_minus_alphas = tables
         total = steps.shape[0]
         eps_fn = _Guided(self.model, conditioning, unconditional_guidance_scale, unconditional_conditioning, steps, size)
         t_all = torch.tensor(steps.copy(), dtype=torch.float32, device=dev)[:, None].expand(total, batch_size).contiguous()
         t_long = t_all.long() if score_corrector is not None else None     # the reference hands the callback `ts` (int64, ddim.py:217)
         inter = {"x_inter": [img], "pred_x0": [img]}
-        paint = _Inpaint(self.model, mask, x0, size, kwargs.get("q_noise_fn"))
         for i in range(total):
             index = total - i - 1
-            if paint.on:                     # ddim.py:206-209
+            if paint is not None and paint.on:      # ddim.py:206-209
                 img = paint.blend(img, steps[i])
-            a_t, a_prev = tb.alphas[index], tb.alphas_prev[index]
+            a_t, a_prev = alphas[index], alphas_prev[index]
             if classifier is None:
                 e_t = eps_fn(img, t_all[i], i)
             else:                            # ddim.py:374-380: the classifier gradient first ...
@@ -232,14 +313,14 @@ class DDIMSampler(object):
                 e_t = score_corrector.modify_score(self.model, e_t, img, t_long[i], conditioning, **(corrector_kwargs or {}))
                 e_t = E._dev_f32(e_t, dev)
                 eps_fn.reclaim_context()
-            sigma = tb.sigmas[index]
+            sigma = sigmas[index]
             noise = None
             if sigma != 0.0:         # ddim.py:269-271: noise * temperature, then dropout of the noise (functional default: training)
                 noise = (noise_fn(size) if noise_fn is not None else torch.randn(size, device=dev)) * temperature
                 if noise_dropout > 0.0:
                     noise = torch.nn.functional.dropout(noise, p=float(noise_dropout))
                 noise = noise.to(dev, torch.float32).contiguous()
-            img, pred_x0 = E.ddim_update(img, e_t, a_t, a_prev, sigma, tb.sqrt_one_minus_alphas[index], noise)
+            img, pred_x0 = E.ddim_update(img, e_t, a_t, a_prev, sigma, sqrt_one_minus_alphas[index], noise)
             if callback:
                 callback(i)
             if img_callback:

@@ -40,7 +40,29 @@ def register_schedule(linear_start, linear_end, timesteps, v_posterior=0.0, beta
         "posterior_mean_coef1": betas * np.sqrt(prev) / (1.0 - acp),
         "posterior_mean_coef2": (1.0 - prev) * np.sqrt(1.0 - betas) / (1.0 - acp),
     }
-    return {k: torch.tensor(v, dtype=torch.float32) for k, v in tab.items()}
+    out = {k: torch.tensor(v, dtype=torch.float32) for k, v in tab.items()}
+    # lvlb_weights (ddpm.py:164-173, eps form): the reference computes this one from its fp32 BUFFERS, in fp32 -- so does this
+    # (a non-persistent buffer there: no checkpoint carries it, and it is not one of BUFFER_NAMES)
+    w = out["betas"] ** 2 / (2 * out["posterior_variance"] * torch.tensor(1.0 - betas, dtype=torch.float32)
+                             * (1 - out["alphas_cumprod"]))
+    w[0] = w[1]
+    out["lvlb_weights"] = w
+    return out
+
+
+def original_step_tables(alphas_cumprod, alphas_cumprod_prev, sqrt_one_minus_alphas_cumprod, eta=0.0):
+    """The use_original_steps=True tables of DDIMSampler (ddim.py:254-257, 404-405), fp32 numpy vectors over all DDPM timesteps.
+    alphas_cumprod / alphas_cumprod_prev / sqrt_one_minus_alphas_cumprod are the MODEL's buffers, which p_sample_ddim reads
+    (ddim.py:253-255); ddim_sigmas_for_original_num_steps is computed from them in fp32, as ddim.py:53-56 does; sqrt_alphas_cumprod
+    and sampler_sqrt_one_minus_alphas_cumprod are the SAMPLER's own fp32 square roots of the fp32 buffer (ddim.py:39-40), which
+    stochastic_encode reads (ddim.py:404-405) -- they differ from the model's fp64-derived buffers in the last bit."""
+    ac = alphas_cumprod.detach().cpu().float()
+    prev = alphas_cumprod_prev.detach().cpu().float()
+    sig = float(eta) * torch.sqrt((1 - prev) / (1 - ac) * (1 - ac / prev))
+    return {"alphas_cumprod": ac.numpy(), "alphas_cumprod_prev": prev.numpy(),
+            "sqrt_one_minus_alphas_cumprod": sqrt_one_minus_alphas_cumprod.detach().cpu().float().numpy(),
+            "ddim_sigmas_for_original_num_steps": sig.numpy(),
+            "sqrt_alphas_cumprod": np.sqrt(ac.numpy()), "sampler_sqrt_one_minus_alphas_cumprod": np.sqrt(1.0 - ac.numpy())}
 
 
 class DDIMTables:

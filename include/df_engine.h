@@ -289,6 +289,29 @@ int df_lincomb(float* out_dev, const float* const* in_dev, const float* coef, in
  * chw per sample, hw per channel); mask is [B][mask_c][H][W] with mask_c = 1 (broadcast over channels) or C.  out != img. */
 int df_q_sample_blend(const float* img_dev, const float* x0_dev, const float* noise_dev, const float* mask_dev, float* out_dev,
                       int64_t n, int64_t chw, int64_t hw, int mask_c, float sqrt_acp, float sqrt_one_minus_acp, void* stream);
+/* The forward process at a PER-SAMPLE timestep (LatentDiffusion.q_sample, ddpm.py:279-282; DDIMSampler.stochastic_encode,
+ * ddim.py:412-413): out[b] = A[t[b]] * x0[b] + S[t[b]] * noise[b].  x0 / noise / out fp32 [B][n] contiguous, t int64 [B] ON THE
+ * DEVICE (a torch.randint result needs no host round trip), A / S fp32 device tables of T entries: the model's sqrt_alphas_cumprod /
+ * sqrt_one_minus_alphas_cumprod, or a sampler's sqrt(ddim_alphas) / ddim_sqrt_one_minus_alphas.  A t[b] outside [0, T) never becomes
+ * an address: that sample's output is NaN in every element and the tables are not read for it.  float4 loads and stores where the
+ * three tensors share an alignment (scalar elements up to the first 16-byte boundary of every sample and behind its last whole
+ * float4), scalar otherwise.  out must not alias x0 or noise.  B, n, T >= 1.  Stateless, like df_lincomb. */
+int df_q_sample(const float* x0_dev, const float* noise_dev, const int64_t* t_dev, const float* A_dev, const float* S_dev,
+                float* out_dev, int B, int64_t n, int T, void* stream);
+/* The denoising loss of LatentDiffusion.p_losses behind its UNet call (get_loss ddpm.py:284-297, the reduction ddpm.py:1061-1079).
+ * pred / target fp32 [B][n], t int64 [B] and the tables logvar / lvlb_weights fp32 [T] on the device; loss_type 0 = l2, 1 = l1.
+ * loss_simple[b] = mean over n of (target - pred)^2 or |target - pred| (:1061), and scalars[5] =
+ *   { mean(loss_simple)                                           loss_simple  (:1062)
+ *     mean(loss_simple / exp(logvar[t]) + logvar[t])              loss_gamma   (:1067-1070)
+ *     mean(lvlb_weights[t] * loss_simple)                         loss_vlb     (:1075-1077)
+ *     l_simple_weight * [1] + original_elbo_weight * [2]          loss         (:1073, 1078-1079)
+ *     mean(logvar) over the T entries                             logvar       (:1071) }.
+ * Two launches: one block per sample (per-lane sums, a DPP tree per wavefront, one LDS step across wavefronts), then one wavefront
+ * that adds the B values in a fixed order.  No atomics: equal inputs give equal bits.  A t[b] outside [0, T) reads no table and
+ * makes loss_simple[b] and scalars[0..3] NaN.  B, n, T >= 1.  Stateless. */
+int df_diffusion_loss(const float* pred_dev, const float* target_dev, const int64_t* t_dev, const float* logvar_dev,
+                      const float* lvlb_weights_dev, float* loss_simple_dev, float* scalars_dev, int B, int64_t n, int T,
+                      int loss_type, float l_simple_weight, float original_elbo_weight, void* stream);
 /* DDIM update (ddim.py:258-272).  noise may be NULL (eta = 0). */
 int df_ddim_update(const float* x_dev, const float* e_dev, const float* noise_dev, float* x_prev_dev,
                    float* pred_x0_dev, int64_t n, float a_t, float a_prev, float sigma_t, float sqrt_one_minus_at,
