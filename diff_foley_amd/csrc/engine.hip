@@ -713,6 +713,25 @@ int df_diffusion_loss(const float* pred, const float* target, const int64_t* t, 
                                  l_simple_weight, original_elbo_weight, (hipStream_t)stream));
   });
 }
+int df_dpm_data_prediction(const float* x, const float* eps, float* out, float* s_out, int B, int64_t n, float alpha, float sigma,
+                           int thresholding, float max_val, void* stream) {
+  return guard([&] {
+    need_positive("dpm_data_prediction", {{"batch", B}});
+    if (n < 1) fail("dpm_data_prediction: %ld elements per sample (at least 1)", (long)n);
+    if (thresholding && n > ((int64_t)1 << 30)) fail("dpm_data_prediction: %ld elements per sample (thresholding: at most 2^30)", (long)n);
+    if (!x || !eps || !out) fail("dpm_data_prediction: null pointer argument");
+    HIPCHK(launch_dpm_data_prediction(x, eps, out, s_out, B, (long)n, alpha, sigma, thresholding ? 1 : 0, max_val, (hipStream_t)stream));
+  });
+}
+int df_dpm_adaptive_error(const float* x_hi, const float* x_lo, const float* x_prev, float* norm, float* out, int B, int64_t n,
+                          float atol, float rtol, void* stream) {
+  return guard([&] {
+    need_positive("dpm_adaptive_error", {{"batch", B}});
+    if (n < 1) fail("dpm_adaptive_error: %ld elements per sample (at least 1)", (long)n);
+    if (!x_hi || !x_lo || !x_prev || !norm || !out) fail("dpm_adaptive_error: null pointer argument");
+    HIPCHK(launch_dpm_adaptive_error(x_hi, x_lo, x_prev, norm, out, B, (long)n, atol, rtol, (hipStream_t)stream));
+  });
+}
 int df_ddim_update(const float* x, const float* e, const float* noise, float* x_prev, float* pred_x0, int64_t n,
                    float a_t, float a_prev, float sigma_t, float sqrt_one_minus_at, void* stream) {
   return guard([&] {

@@ -95,6 +95,14 @@ hipError_t launch_q_sample(const float* x0, const float* noise, const long long*
 hipError_t launch_diffusion_loss(const float* pred, const float* target, const long long* t, const float* logvar, const float* lvlb,
                                  float* loss_simple, float* scalars, int B, long n, int T, int loss_type, float l_simple_weight,
                                  float original_elbo_weight, hipStream_t s);
+// out = (x - sigma eps) / alpha over [B][n]; thresholding: per sample s = max(quantile_0.995(|x0|), max_val) by an exact radix select,
+// out = clamp(x0, -s, s) / s, s_out[b] = s (s_out may be NULL); a NaN in a sample makes that sample NaN (dpm.hip)
+hipError_t launch_dpm_data_prediction(const float* x, const float* eps, float* out, float* s_out, int B, long n, float alpha,
+                                      float sigma, int thresholding, float max_val, hipStream_t s);
+// out[0] = max_b sqrt(mean_i(((x_hi - x_lo) / max(atol, rtol max(|x_lo|, |x_prev|)))^2)); norm[B] is the per-sample value; two
+// launches, fixed summation order, no atomics (dpm.hip)
+hipError_t launch_dpm_adaptive_error(const float* x_hi, const float* x_lo, const float* x_prev, float* norm, float* out, int B, long n,
+                                     float atol, float rtol, hipStream_t s);
 
 // Row softmax: fp32 scores [rows][T] -> bf16 probabilities [rows][T]  (VAE single-head attention)
 // p rows have ldp >= T elements; columns [T, ldp) are written as zeros (the K padding of the P V GEMM)

@@ -166,6 +166,8 @@ _SIGS = {
                           C.c_float, C.c_float, C.c_void_p],
     "df_q_sample": [C.c_void_p] * 6 + [C.c_int, C.c_int64, C.c_int, C.c_void_p],
     "df_diffusion_loss": [C.c_void_p] * 7 + [C.c_int, C.c_int64, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p],
+    "df_dpm_data_prediction": [C.c_void_p] * 4 + [C.c_int, C.c_int64, C.c_float, C.c_float, C.c_int, C.c_float, C.c_void_p],
+    "df_dpm_adaptive_error": [C.c_void_p] * 5 + [C.c_int, C.c_int64, C.c_float, C.c_float, C.c_void_p],
     "df_ddim_update": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float,
                        C.c_float, C.c_float, C.c_void_p],
     "df_plan_count": [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
@@ -1083,6 +1085,42 @@ def diffusion_loss(pred, target, t, logvar, lvlb_weights, loss_type="l2", l_simp
                                  pred.numel() // B, lv.numel(), LOSS_TYPES[loss_type], float(l_simple_weight),
                                  float(original_elbo_weight), _stream()))
     return loss_simple, scalars
+
+
+def dpm_data_prediction(x, eps, alpha, sigma, thresholding=False, max_val=1.0, return_s=False):
+    """x0 = (x - sigma * eps) / alpha over fp32 [B][...] (dpm_solver.py:386-393); thresholding: per sample
+    s = max(quantile_0.995(|x0|), max_val), x0 = clamp(x0, -s, s) / s (:394-398) -- df_dpm_data_prediction.  return_s: (x0, s [B])."""
+    dev = x.device
+    x = _dev_f32(x, dev)
+    if tuple(eps.shape) != tuple(x.shape):
+        raise ValueError(f"dpm_data_prediction: eps of shape {tuple(eps.shape)}, expected {tuple(x.shape)} (the shape of x)")
+    eps = _dev_f32(eps, dev)
+    B = int(x.shape[0]) if x.ndim else 0
+    out = torch.empty_like(x)
+    s = torch.empty(B, device=dev, dtype=torch.float32) if return_s else None
+    if out.numel() > 0:
+        _chk(lib().df_dpm_data_prediction(_ptr(x), _ptr(eps), _ptr(out), _ptr(s) if return_s else None, B, out.numel() // B,
+                                          float(alpha), float(sigma), 1 if thresholding else 0, float(max_val), _stream()))
+    return (out, s) if return_s else out
+
+
+def dpm_adaptive_error(x_hi, x_lo, x_prev, atol, rtol):
+    """(E [1], norm [B]) of df_dpm_adaptive_error, fp32 on x_hi's device and not read here:
+    norm[b] = sqrt(mean(((x_hi - x_lo) / max(atol, rtol * max(|x_lo|, |x_prev|)))^2)), E = max_b norm[b] (dpm_solver.py:952-954)."""
+    dev = x_hi.device
+    x_hi = _dev_f32(x_hi, dev)
+    for name, v in (("x_lo", x_lo), ("x_prev", x_prev)):
+        if tuple(v.shape) != tuple(x_hi.shape):
+            raise ValueError(f"dpm_adaptive_error: {name} of shape {tuple(v.shape)}, expected {tuple(x_hi.shape)} (the shape of x_hi)")
+    x_lo, x_prev = _dev_f32(x_lo, dev), _dev_f32(x_prev, dev)
+    B = int(x_hi.shape[0]) if x_hi.ndim else 0
+    if x_hi.numel() == 0:
+        raise ValueError("dpm_adaptive_error: empty input")
+    norm = torch.empty(B, device=dev, dtype=torch.float32)
+    out = torch.empty(1, device=dev, dtype=torch.float32)
+    _chk(lib().df_dpm_adaptive_error(_ptr(x_hi), _ptr(x_lo), _ptr(x_prev), _ptr(norm), _ptr(out), B, x_hi.numel() // B, float(atol),
+                                     float(rtol), _stream()))
+    return out, norm
 
 
 def ddim_update(x, e, a_t, a_prev, sigma_t, sqrt_one_minus_at, noise=None):

@@ -444,6 +444,23 @@ class LatentDiffusion(_EngineModel):
     def _sampler(self, name):
         return {"DDIM": S.DDIMSampler, "DPM_Solver": S.DPMSolverSampler, "PLMS": S.PLMSSampler}[name](self)
 
+    def dpm_solver(self, cond, unconditional_guidance_scale=1.0, unconditional_conditioning=None, classifier=None, origin_cond=None,
+                   classifier_guide_scale=0.0, predict_x0=True, thresholding=False, max_val=1.):
+        """A dpm_solver.DPM_Solver over this model on the fast route (the guided evaluation of the samplers, time embedding hoisted):
+        what dpm_solver/sampler.py:50-80 builds, with the whole family behind ``.sample(x, steps=..., order=..., method=...)``.
+        ``classifier`` (an AlignmentClassifier) with ``origin_cond`` selects double guidance."""
+        from . import dpm_solver as D
+        ns = D.NoiseScheduleVP('discrete', alphas_cumprod=self.alphas_cumprod)
+        if classifier is None:
+            fn = D.model_wrapper(self.apply_model, ns, model_type="noise", guidance_type="classifier-free", condition=cond,
+                                 unconditional_condition=unconditional_conditioning, guidance_scale=unconditional_guidance_scale)
+        else:
+            fn = D.model_wrapper_with_classifier(self.apply_model, ns, model_type="noise", guidance_type="double-guide", condition=cond,
+                                                 origin_cond=origin_cond, unconditional_condition=unconditional_conditioning,
+                                                 guidance_scale=unconditional_guidance_scale, classifier=classifier,
+                                                 classifier_guide_scale=classifier_guide_scale)
+        return D.DPM_Solver(fn, ns, predict_x0=predict_x0, thresholding=thresholding, max_val=max_val)
+
     @_locked
     @torch.no_grad()
     def sample_log(self, cond, batch_size, ddim, ddim_steps, size_len=64, unconditional_guidance_scale=1.0,

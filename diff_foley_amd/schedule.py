@@ -94,11 +94,15 @@ class DDIMTables:
 class DPMTables:
     """Piece-wise linear log(alpha_t) of NoiseScheduleVP('discrete') in fp32 (dpm_solver.py:99-174, 1132-1171)."""
 
-    def __init__(self, alphas_cumprod):
-        ac = alphas_cumprod.detach().cpu().float()
-        self.N = ac.shape[0]
+    def __init__(self, alphas_cumprod=None, betas=None):
+        if betas is not None:             # dpm_solver.py:100-101: betas win when both are given
+            la = 0.5 * torch.log(1 - betas.detach().cpu().float()).cumsum(dim=0)
+        else:
+            assert alphas_cumprod is not None
+            la = 0.5 * torch.log(alphas_cumprod.detach().cpu().float())
+        self.N = la.shape[0]
         self.t_knots = torch.linspace(0.0, 1.0, self.N + 1)[1:].numpy().astype(np.float32)
-        self.la_knots = (0.5 * torch.log(ac)).numpy().astype(np.float32)
+        self.la_knots = la.numpy().astype(np.float32)
 
     def log_alpha(self, t):
         t = np.float32(t)
@@ -124,3 +128,60 @@ class DPMTables:
 
     def time_steps(self, S):
         return torch.linspace(1.0, 1.0 / self.N, S + 1).numpy().astype(np.float32)
+
+    T = 1.0
+    schedule = "discrete"
+
+    def inverse_lambda(self, lamb):
+        """t of a half-logSNR (dpm_solver.py:166-169): log(alpha) = -0.5 logaddexp(0, -2 lambda), then the same piece-wise linear
+        map read the other way round (knots in ascending log(alpha), i.e. flipped)."""
+        la = np.float32(-0.5) * np.logaddexp(np.float32(0.0), np.float32(-2.0) * np.float32(lamb))
+        xk, yk = self.la_knots[::-1], self.t_knots[::-1]
+        i = int(np.searchsorted(xk, la, side="left"))
+        lo = 0 if i == 0 else (self.N - 2 if i == self.N else i - 1)
+        x0, x1, y0, y1 = xk[lo], xk[lo + 1], yk[lo], yk[lo + 1]
+        return np.float32(y0 + (la - x0) * (y1 - y0) / (x1 - x0))
+
+
+class ContinuousTables:
+    """NoiseScheduleVP('linear' | 'cosine') on fp32 host scalars (dpm_solver.py:110-123, 131-136, 162-174): the interface of
+    DPMTables for the two continuous-time VP schedules."""
+
+    N = 1000
+
+    def __init__(self, schedule, beta_0=0.1, beta_1=20.0):
+        if schedule not in ("linear", "cosine"):
+            raise ValueError(f"Unsupported noise schedule {schedule}. The schedule needs to be 'discrete' or 'linear' or 'cosine'")
+        self.schedule = schedule
+        self.beta_0, self.beta_1 = beta_0, beta_1
+        self.cosine_s = 0.008
+        self.cosine_beta_max = 999.0
+        self.cosine_t_max = math.atan(self.cosine_beta_max * (1.0 + self.cosine_s) / math.pi) * 2.0 * (1.0 + self.cosine_s) / math.pi \
+            - self.cosine_s
+        self.cosine_log_alpha_0 = math.log(math.cos(self.cosine_s / (1.0 + self.cosine_s) * math.pi / 2.0))
+        self.T = 0.9946 if schedule == "cosine" else 1.0      # T = 1 has numerical issues on the cosine schedule (the reference's words)
+
+    def log_alpha(self, t):
+        t = np.float32(t)
+        if self.schedule == "linear":
+            return np.float32(np.float32(-0.25) * t ** 2 * np.float32(self.beta_1 - self.beta_0) - np.float32(0.5) * t * np.float32(self.beta_0))
+        c = np.cos((t + np.float32(self.cosine_s)) / np.float32(1.0 + self.cosine_s) * np.float32(math.pi) / np.float32(2.0))
+        return np.float32(np.log(c) - np.float32(self.cosine_log_alpha_0))
+
+    alpha = DPMTables.alpha
+    sigma = DPMTables.sigma
+    lam = DPMTables.lam
+
+    def model_time(self, t):
+        return np.float32(t)          # continuous-time models take t itself (dpm_solver.py:286-287)
+
+    def inverse_lambda(self, lamb):
+        lamb = np.float32(lamb)
+        if self.schedule == "linear":
+            tmp = np.float32(2.0 * (self.beta_1 - self.beta_0)) * np.logaddexp(np.float32(-2.0) * lamb, np.float32(0.0))
+            delta = np.float32(self.beta_0 ** 2) + tmp
+            return np.float32(tmp / (np.sqrt(delta) + np.float32(self.beta_0)) / np.float32(self.beta_1 - self.beta_0))
+        la = np.float32(-0.5) * np.logaddexp(np.float32(-2.0) * lamb, np.float32(0.0))
+        t = np.arccos(np.exp(la + np.float32(self.cosine_log_alpha_0))) * np.float32(2.0) * np.float32(1.0 + self.cosine_s) \
+            / np.float32(math.pi) - np.float32(self.cosine_s)
+        return np.float32(t)

@@ -312,6 +312,22 @@ int df_q_sample(const float* x0_dev, const float* noise_dev, const int64_t* t_de
 int df_diffusion_loss(const float* pred_dev, const float* target_dev, const int64_t* t_dev, const float* logvar_dev,
                       const float* lvlb_weights_dev, float* loss_simple_dev, float* scalars_dev, int B, int64_t n, int T,
                       int loss_type, float l_simple_weight, float original_elbo_weight, void* stream);
+/* The data prediction of DPM-Solver++ (DPM_Solver.data_prediction_fn, dpm_solver.py:386-399): out = (x - sigma * eps) / alpha over
+ * fp32 [B][n], alpha / sigma the schedule's values at the step's time.  thresholding != 0 adds Imagen's dynamic thresholding per
+ * sample: s = max(quantile_0.995(|x0|), max_val), out = clamp(x0, -s, s) / s.  The quantile follows torch.quantile's 'linear' rule
+ * (rank 0.995 (n - 1) in fp32, linear interpolation between the two neighbouring order statistics) and is an exact selection: a
+ * four-pass radix select on the bit patterns of |x0| with 256-bin histograms in LDS, one block per sample, x0 re-evaluated
+ * identically in every pass.  s_out (fp32 [B], may be NULL) receives s.  A NaN anywhere in a sample makes s and the whole sample
+ * NaN, as torch.quantile does.  Integer LDS atomics only: equal inputs give equal bits.  out must not alias x or eps.  B, n >= 1;
+ * with thresholding n <= 2^30.  Stateless, like df_lincomb. */
+int df_dpm_data_prediction(const float* x_dev, const float* eps_dev, float* out_dev, float* s_out_dev, int B, int64_t n, float alpha,
+                           float sigma, int thresholding, float max_val, void* stream);
+/* The error estimate of the adaptive DPM-Solver (dpm_solver_adaptive, dpm_solver.py:952-954):
+ * out[0] = max over b of norm[b], norm[b] = sqrt(mean_i(((x_hi - x_lo) / max(atol, rtol * max(|x_lo|, |x_prev|)))^2)); all tensors
+ * fp32 [B][n] on the device, norm fp32 [B] and out fp32 [1] on the device (the driver reads out).  One block per sample, then one
+ * wavefront over the batch: no atomics, fixed summation order.  A NaN norm makes out NaN.  B, n >= 1.  Stateless. */
+int df_dpm_adaptive_error(const float* x_hi_dev, const float* x_lo_dev, const float* x_prev_dev, float* norm_dev, float* out_dev,
+                          int B, int64_t n, float atol, float rtol, void* stream);
 /* DDIM update (ddim.py:258-272).  noise may be NULL (eta = 0). */
 int df_ddim_update(const float* x_dev, const float* e_dev, const float* noise_dev, float* x_prev_dev,
                    float* pred_x0_dev, int64_t n, float a_t, float a_prev, float sigma_t, float sqrt_one_minus_at,
