@@ -9,9 +9,9 @@ from . import schedule  # noqa: F401
 from . import engine  # noqa: F401
 from .ldm import (LatentDiffusion, AlignmentClassifier, AlignmentClassifierMetric, CAVPInference,  # noqa: F401
                   DiagonalGaussianDistribution, instantiate_from_config)
-from .samplers import DDIMSampler, PLMSSampler, DPMSolverSampler  # noqa: F401
+from .samplers import DDIMSampler, PLMSSampler  # noqa: F401
 from . import dpm_solver  # noqa: F401
-from .dpm_solver import NoiseScheduleVP, DPM_Solver, model_wrapper, model_wrapper_with_classifier  # noqa: F401
+from .dpm_solver import DPMSolverSampler, NoiseScheduleVP, DPM_Solver, model_wrapper, model_wrapper_with_classifier  # noqa: F401
 from .video import ExtractCAVPFeatures, frames_to_tensor  # noqa: F401
 from .vocoder import get_spectrogram, inverse_op, mel_to_wave, wave_to_mel  # noqa: F401
 

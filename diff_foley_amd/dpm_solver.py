@@ -1,11 +1,12 @@
 """The DPM-Solver family of the reference (diff_foley/models/diffusion/dpm_solver/dpm_solver.py) on the MI355X path: NoiseScheduleVP,
 model_wrapper / model_wrapper_with_classifier and DPM_Solver with orders 1-3, the singlestep / singlestep_fixed / multistep /
 adaptive methods, three step spacings, noise and data prediction, both expansions, t_start / t_end, denoise_to_zero and dynamic
-thresholding -- behind the reference's names and parameter lists.
+thresholding -- behind the reference's names and parameter lists; and DPMSolverSampler (dpm_solver/sampler.py), the samplers' call
+surface over the solver's DPM-Solver++(2M) configuration.
 
-How it runs.  Times and every coefficient are fp32 scalars ON THE HOST (schedule.DPMTables / ContinuousTables), as in
-samplers.DPMSolverSampler; each solver update is one ``df_lincomb`` of at most four tensors (the D1 / D2 differences of the
-third-order formulas are expanded into the model values they are made of), the thresholded data prediction is
+How it runs.  Times and every coefficient are fp32 scalars ON THE HOST (schedule.DPMTables / ContinuousTables); each solver update is
+one ``df_lincomb`` of at most four tensors (the D1 / D2 differences of the third-order formulas are expanded into the model values
+they are made of), the thresholded data prediction is
 ``df_dpm_data_prediction`` and the adaptive solver's error estimate ``df_dpm_adaptive_error``.  ``s`` / ``t`` arguments may be floats,
 0-d tensors or (B,) tensors with equal entries; a device tensor is read once; unequal entries raise ValueError (the host drives one
 time for the whole batch).  ``sample()`` itself waits for the device nowhere -- except ``method='adaptive'``, which reads one float
@@ -34,7 +35,7 @@ import numpy as np
 import torch
 
 from . import engine as E
-from . import samplers as S
+from . import samplers
 from .schedule import ContinuousTables, DPMTables
 
 F = np.float32
@@ -163,7 +164,7 @@ class _WrappedModel:
     def _grad(self, classifier, x, t, cond):
         t_input = self._t_input(t, x.shape[0], x.device)
         if self.fast_model is not None:
-            return S._classifier_grad(self.fast_model, classifier, x, t_input, cond)
+            return samplers._classifier_grad(self.fast_model, classifier, x, t_input, cond)
         return classifier.log_prob_grad(x, t_input, cond)
 
     def _eval(self, x, t):
@@ -215,7 +216,7 @@ class _FastSession:
         self.double = w.guidance_type == "double-guide" and w.classifier is not None and w.cfg
         if self.double and getattr(w.classifier, "engine", 1) is None:
             w.classifier.attach(self.m)      # loading its tensors re-finalises the engine: before the context and the table are set
-        self.eps = S._Guided(self.m, w.condition, w.guidance_scale, w.unconditional_condition, t_model, tuple(x_shape))
+        self.eps = samplers._Guided(self.m, w.condition, w.guidance_scale, w.unconditional_condition, t_model, tuple(x_shape))
 
     def __call__(self, x, t):
         x = E._dev_f32(x, self.m.device)
@@ -225,8 +226,8 @@ class _FastSession:
         if not self.double:
             return self.eps(x, t_in, k)
         w = self.w                                                 # double guidance (dpm_solver.py:1377-1393)
-        noise, g = S._eps_and_classifier_grad(self.m, w.classifier, lambda: self.eps(x, t_in, k), x, t_in, w.origin_cond)
-        return E.lincomb([(1.0, noise), (-w.classifier_guide_scale * self.tb.sigma(t), g)])
+        return samplers._classifier_guided_eps(self.m, w.classifier, lambda: self.eps(x, t_in, k), x, t_in, w.origin_cond,
+                                        w.classifier_guide_scale * self.tb.sigma(t))
 
 
 def model_wrapper(model, noise_schedule, model_type="noise", model_kwargs={}, guidance_type="uncond", condition=None,
@@ -464,7 +465,7 @@ class DPM_Solver:
         r0 = h0 / h
         if self.predict_x0:
             k = ns.alpha(t) * (np.exp(-h) - np.float32(1.0))
-            if solver_type == 'dpm_solver':      # x_t = sig_t/sig_0 x - k m0 - 0.5 k (m0 - m1)/r0: DPMSolverSampler's very expression
+            if solver_type == 'dpm_solver':      # x_t = sig_t/sig_0 x - k m0 - 0.5 k (m0 - m1)/r0: the update of DPM-Solver++(2M)
                 return E.lincomb([(ns.sigma(t) / ns.sigma(t0), x), (-k - 0.5 * k / r0, m0), (0.5 * k / r0, m1)])
             d = ns.alpha(t) * ((np.exp(-h) - F(1.0)) / h + F(1.0)) / r0
             return E.lincomb([(ns.sigma(t) / ns.sigma(t0), x), (-k + d, m0), (-d, m1)])
@@ -649,3 +650,34 @@ class DPM_Solver:
             return x
         finally:
             self._session = None
+
+
+class DPMSolverSampler(object):
+    """dpm_solver/sampler.py:11-156: DPM-Solver++(2M) behind the samplers' call surface -- the model's DPM_Solver (fast route) with
+    multistep, order 2, time_uniform, predict_x0 and lower_order_final, which acts only if S < 15."""
+
+    def __init__(self, model, **kwargs):
+        self.model = model
+
+    @torch.no_grad()
+    def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None,
+               quantize_x0=False, eta=0.0, mask=None, x0=None, temperature=1.0, noise_dropout=0.0, score_corrector=None,
+               corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, unconditional_guidance_scale=1.0,
+               unconditional_conditioning=None, classifier=None, origin_cond=None, classifier_guide_scale=0.0, **kwargs):
+        # the reference's parameters in the reference's order (sampler.py:25-48), then the three of sample_with_classifier.  The
+        # reference ignores eta / temperature / noise_dropout, the callbacks and log_every_t here (sampler.py:24-56 passes none of
+        # them to DPM_Solver): same
+        samplers.reject_unsupported("DPMSolverSampler", dict(kwargs, quantize_x0=quantize_x0, mask=mask, x0=x0, score_corrector=score_corrector),
+                                    dict(mask=None, x0=None, score_corrector=None))   # sampler.py:24-56 accepts and drops them
+        samplers._warn_batch(conditioning, batch_size)
+        x, _ = samplers._start(self.model, batch_size, shape, x_T)
+        solver = self.model.dpm_solver(conditioning, unconditional_guidance_scale, unconditional_conditioning, classifier, origin_cond,
+                                       classifier_guide_scale)
+        return solver.sample(x, steps=S, order=2, skip_type="time_uniform", method="multistep", lower_order_final=True), None
+
+    sample_with_classifier = samplers.sample_with_classifier
+
+
+# The class lived in samplers.py before it became a client of DPM_Solver; that spelling keeps resolving for callers written against
+# it.  Set from here, the one direction the dependency runs: samplers.py knows nothing of this module.
+samplers.DPMSolverSampler = DPMSolverSampler

@@ -708,7 +708,8 @@ class Engine:
         _chk(self.L.df_unet_set_timesteps(self._h, ts, len(timesteps), int(batch), int(H), int(W), 1 if cfg else 0, self._on("unet")),
              self.L)
 
-    def unet_forward(self, x, t, out=None, ts_index=None):
+    def _unet(self, x, t, out, ts_index, scale=None):
+        """unet_forward (scale None) and unet_forward_cfg: one of the four ABI entries, by guidance and by ts_index."""
         x = _dev_f32(x, self.device)
         unet = self.configured.of("unet")
         _want_nchw("UNet input", x, unet.in_channels)
@@ -717,29 +718,19 @@ class Engine:
             out = torch.empty(N, unet.out_channels, H, W, device=self.device, dtype=torch.float32)
         if N == 0:                # an empty batch is an empty result (torch modules accept it; no plan exists for it)
             return out
-        if ts_index is not None:
-            _chk(self.L.df_unet_forward_ts(self._h, _ptr(x), int(ts_index), _ptr(out), N, H, W, self._on("unet")), self.L)
-            return out
-        t = _timesteps(t, N, self.device)
-        _chk(self.L.df_unet_forward(self._h, _ptr(x), _ptr(t), _ptr(out), N, H, W, self._on("unet")), self.L)
+        fn = getattr(self.L, "df_unet_forward" + ("" if scale is None else "_cfg") + ("" if ts_index is None else "_ts"))
+        if ts_index is None:
+            t = _timesteps(t, N, self.device)
+        at = _ptr(t) if ts_index is None else int(ts_index)
+        guidance = () if scale is None else (float(scale),)
+        _chk(fn(self._h, _ptr(x), at, _ptr(out), N, H, W, *guidance, self._on("unet")), self.L)
         return out
 
+    def unet_forward(self, x, t, out=None, ts_index=None):
+        return self._unet(x, t, out, ts_index)
+
     def unet_forward_cfg(self, x, t, scale, out=None, ts_index=None):
-        x = _dev_f32(x, self.device)
-        unet = self.configured.of("unet")
-        _want_nchw("UNet input", x, unet.in_channels)
-        B, Cc, H, W = x.shape
-        if out is None:
-            out = torch.empty(B, unet.out_channels, H, W, device=self.device, dtype=torch.float32)
-        if B == 0:
-            return out
-        if ts_index is not None:
-            _chk(self.L.df_unet_forward_cfg_ts(self._h, _ptr(x), int(ts_index), _ptr(out), B, H, W, float(scale), self._on("unet")),
-                 self.L)
-            return out
-        t = _timesteps(t, B, self.device)
-        _chk(self.L.df_unet_forward_cfg(self._h, _ptr(x), _ptr(t), _ptr(out), B, H, W, float(scale), self._on("unet")), self.L)
-        return out
+        return self._unet(x, t, out, ts_index, scale)
 
     def vae_decode(self, z):
         z = _dev_f32(z, self.device)

@@ -21,6 +21,7 @@ import importlib
 
 import torch
 
+from . import dpm_solver as D
 from . import engine as E
 from . import samplers as S
 from .align_metric import (AlignmentClassifierMetric, _MetricBackboneFacade, _MetricCondFacade,  # noqa: F401
@@ -442,14 +443,13 @@ class LatentDiffusion(_EngineModel):
     __call__ = forward
 
     def _sampler(self, name):
-        return {"DDIM": S.DDIMSampler, "DPM_Solver": S.DPMSolverSampler, "PLMS": S.PLMSSampler}[name](self)
+        return {"DDIM": S.DDIMSampler, "DPM_Solver": D.DPMSolverSampler, "PLMS": S.PLMSSampler}[name](self)
 
     def dpm_solver(self, cond, unconditional_guidance_scale=1.0, unconditional_conditioning=None, classifier=None, origin_cond=None,
                    classifier_guide_scale=0.0, predict_x0=True, thresholding=False, max_val=1.):
         """A dpm_solver.DPM_Solver over this model on the fast route (the guided evaluation of the samplers, time embedding hoisted):
         what dpm_solver/sampler.py:50-80 builds, with the whole family behind ``.sample(x, steps=..., order=..., method=...)``.
         ``classifier`` (an AlignmentClassifier) with ``origin_cond`` selects double guidance."""
-        from . import dpm_solver as D
         ns = D.NoiseScheduleVP('discrete', alphas_cumprod=self.alphas_cumprod)
         if classifier is None:
             fn = D.model_wrapper(self.apply_model, ns, model_type="noise", guidance_type="classifier-free", condition=cond,

@@ -1,4 +1,4 @@
-"""Sampler host loops of the MI355X path: DDIM, DPM-Solver++(2M), PLMS, ancestral DDPM.
+"""Sampler host loops of the MI355X path: DDIM, PLMS, ancestral DDPM -- and the guided evaluation every sampler shares.
 
 Same call surface as the reference sampler classes (``DDIMSampler(model).sample(S, batch_size, shape,
 conditioning, ...) -> (samples, intermediates)``), but every tensor operation in the loop is a HIP
@@ -7,8 +7,7 @@ guidance combine) and the solver updates (``df_ddim_update`` / ``df_lincomb``). 
 context is handed to the engine once per ``sample()`` (it is step-invariant), so the K/V projections
 of the 16 SpatialTransformers leave the step loop.  torch is used for RNG (x_T, eta noise) only.
 
-Reference: diff_foley/models/diffusion/ddim.py:58-273, plms.py:60-236,
-dpm_solver/sampler.py:24-156 + dpm_solver/dpm_solver.py:504-549,755-810,1071-1105, ddpm.py:1083-1268.
+Reference: diff_foley/models/diffusion/ddim.py:58-273, plms.py:60-236, ddpm.py:1083-1268.
 """
 import numpy as np
 import warnings
@@ -16,7 +15,7 @@ import warnings
 import torch
 
 from . import engine as E
-from .schedule import DDIMTables, DPMTables, original_step_tables
+from .schedule import DDIMTables, original_step_tables
 
 import os as _os
 _NO_HOIST = bool(int(_os.environ.get("DF_NO_THOIST", "0")))      # A/B switch: time embedding inside every step
@@ -32,11 +31,11 @@ def _warn_batch(conditioning, batch_size):
 
 
 # Reference sampler features that are NOT on this path.  The reference classes accept them (ddim.py:58-113, 179-273;
-# plms.py:60-110; dpm_solver/sampler.py:24-56); silently dropping one would return a plausible but wrong sample, so a
-# non-default value raises.  Anything not listed is ignored exactly like the reference's own **kwargs.
+# plms.py:60-110); silently dropping one would return a plausible but wrong sample, so a non-default value raises.  Anything not
+# listed is ignored exactly like the reference's own **kwargs.
 # (`normals_sequence` is accepted and never read by the reference's samplers -- ddim.py:65,123, plms.py:64 -- so it is ignored here too.)
 # (`noise_dropout` IS on the path since round 5: DDIMSampler applies it as ddim.py:270-271 does; with PLMS -- eta = 0, no noise --
-# and DPM-Solver++ -- whose reference sampler drops the argument -- it has nothing to act on and is accepted like the reference.)
+# it has nothing to act on and is accepted like the reference.)
 _UNSUPPORTED_DEFAULTS = dict(quantize_x0=False)
 
 
@@ -155,7 +154,7 @@ _side_streams = {}
 
 
 def _eps_and_classifier_grad(model, classifier, eps_call, x, t, origin_cond):
-    """eps(x, t) and the classifier's d log p / d x at the same (x, t) (ddim.py:374-380, dpm_solver.py:1377-1393) do not depend on
+    """eps(x, t) and the classifier's d log p / d x at the same (x, t) (ddim.py:374-380) do not depend on
     each other, so the gradient's launches go to a second HIP stream beside the UNet step's (round 6).  The gradient plan is ~160
     launches of small grids at the launch floor (1.14 ms per call at B = 8, profiles/r6_classifier_grad_ops.txt); beside the UNet step
     they run on CUs the step's kernels leave idle: configs[2] 152.5 -> 171.1 steps/s, latents bit-equal to the one-stream order
@@ -177,6 +176,89 @@ def _eps_and_classifier_grad(model, classifier, eps_call, x, t, origin_cond):
     cur.wait_stream(side)
     g.record_stream(cur)
     return e, g
+
+
+def _classifier_guided_eps(model, classifier, eps_call, x, t, origin_cond, coef):
+    """eps - coef * d log p / d x: the classifier's half of double guidance (ddim.py:374-380).  ``coef`` is the caller's own
+    sigma_t * classifier_guide_scale, a host scalar."""
+    e, g = _eps_and_classifier_grad(model, classifier, eps_call, x, t, origin_cond)
+    return E.lincomb([(1.0, e), (-coef, g)])
+
+
+def _start(model, batch_size, shape, x_T):
+    """(the start latent, its size): x_T, or noise from the device generator."""
+    C, H, W = shape
+    size = (batch_size, C, H, W)
+    return (torch.randn(size, device=model.device) if x_T is None else x_T.to(model.device, torch.float32).contiguous()), size
+
+
+def _ddim_steps(model, img, size, steps, tables, conditioning, unconditional_guidance_scale, unconditional_conditioning, noise_fn=None,
+                temperature=1.0, noise_dropout=0.0, score_corrector=None, corrector_kwargs=None, classifier=None, origin_cond=None,
+                classifier_guide_scale=0.0, callback=None, img_callback=None, log_every_t=100, paint=None, combine=None):
+    """The step loop of the DDIM family (ddim.py:179-229 with p_sample_ddim :231-273; plms.py:113-236): ``steps`` are the timestep
+    values in visiting order, ``tables`` = (alphas, alphas_prev, sigmas, sqrt_one_minus_alphas) indexed by len(steps) - 1 - i at step i.
+    DDIMSampler.sample() walks the whole DDIM schedule, decode() a prefix of it (or of the original steps), PLMSSampler.sample() the
+    whole schedule with ``combine(e_t, i, eps_at, update) -> eps`` between the evaluation and the update: ``eps_at(x, k)`` is the
+    evaluation at step k, ``update(e)`` the step's df_ddim_update from the current latent."""
+    dev = model.device
+    batch_size = size[0]
+    alphas, alphas_prev, sigmas, sqrt_one_minus_alphas = tables
+    total = steps.shape[0]
+    guided = _Guided(model, conditioning, unconditional_guidance_scale, unconditional_conditioning, steps, size)
+    t_all = torch.tensor(steps.copy(), dtype=torch.float32, device=dev)[:, None].expand(total, batch_size).contiguous()
+    t_long = t_all.long() if score_corrector is not None else None     # the reference hands the callback `ts` (int64, ddim.py:217)
+
+    def eps_at(x, k):
+        if classifier is None:
+            e = guided(x, t_all[k], k)
+        else:                            # ddim.py:374-380: the classifier gradient first ...
+            e = _classifier_guided_eps(model, classifier, lambda: guided(x, t_all[k], k), x, t_all[k], origin_cond,
+                                       np.sqrt(np.float32(1.0) - alphas[total - k - 1]) * classifier_guide_scale)
+        if score_corrector is not None:  # ... then the caller's callback on the guided eps (ddim.py:249-251, 382-384; plms.py:178-190)
+            e = E._dev_f32(score_corrector.modify_score(model, e, x, t_long[k], conditioning, **(corrector_kwargs or {})), dev)
+            guided.reclaim_context()
+        return e
+
+    inter = {"x_inter": [img], "pred_x0": [img]}
+    for i in range(total):
+        index = total - i - 1
+        if paint is not None and paint.on:      # ddim.py:206-209, plms.py:147-150
+            img = paint.blend(img, steps[i])
+        e_t = eps_at(img, i)
+        sigma = sigmas[index]
+        noise = None
+        if sigma != 0.0:         # ddim.py:269-271: noise * temperature, then dropout of the noise (functional default: training)
+            noise = (noise_fn(size) if noise_fn is not None else torch.randn(size, device=dev)) * temperature
+            if noise_dropout > 0.0:
+                noise = torch.nn.functional.dropout(noise, p=float(noise_dropout))
+            noise = noise.to(dev, torch.float32).contiguous()
+        update = lambda e: E.ddim_update(img, e, alphas[index], alphas_prev[index], sigma, sqrt_one_minus_alphas[index], noise)
+        if combine is not None:
+            e_t = combine(e_t, i, eps_at, update)
+        img, pred_x0 = update(e_t)
+        if callback:
+            callback(i)
+        if img_callback:
+            img_callback(pred_x0, i)
+        if index % log_every_t == 0 or index == total - 1:
+            inter["x_inter"].append(img)
+            inter["pred_x0"].append(pred_x0)
+    return img, inter
+
+
+def sample_with_classifier(self, S, batch_size, shape, conditioning=None, origin_cond=None, callback=None, normals_sequence=None,
+                           img_callback=None, quantize_x0=False, eta=0.0, mask=None, x0=None, temperature=1.0, noise_dropout=0.0,
+                           score_corrector=None, corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100,
+                           unconditional_guidance_scale=1.0, unconditional_conditioning=None, classifier=None,
+                           classifier_guide_scale=0.0, **kwargs):
+    """The method of that name of the samplers that take a classifier (ddim.py:115-177 and its twin beside the solver): the
+    reference's parameter list, forwarded to ``sample``, which takes the three classifier arguments itself."""
+    return self.sample(S, batch_size, shape, conditioning, callback=callback, normals_sequence=normals_sequence,
+                       img_callback=img_callback, quantize_x0=quantize_x0, eta=eta, mask=mask, x0=x0, temperature=temperature,
+                       noise_dropout=noise_dropout, score_corrector=score_corrector, corrector_kwargs=corrector_kwargs,
+                       verbose=verbose, x_T=x_T, log_every_t=log_every_t, unconditional_guidance_scale=unconditional_guidance_scale,
+                       unconditional_conditioning=unconditional_conditioning, classifier=classifier, origin_cond=origin_cond,
+                       classifier_guide_scale=classifier_guide_scale, **kwargs)
 
 
 class DDIMSampler(object):
@@ -258,7 +340,7 @@ class DDIMSampler(object):
         x = E._dev_f32(x_latent, self.model.device)
         if x.ndim != 4:
             raise ValueError(f"decode: x_latent of shape {tuple(x.shape)}, expected [B][C][H][W]")
-        x_dec, _ = self._steps(x, tuple(x.shape), np.flip(timesteps), tables, cond, unconditional_guidance_scale,
+        x_dec, _ = _ddim_steps(self.model, x, tuple(x.shape), np.flip(timesteps), tables, cond, unconditional_guidance_scale,
                                unconditional_conditioning, noise_fn=getattr(self, "noise_fn", None))
         return x_dec
 
@@ -273,74 +355,16 @@ class DDIMSampler(object):
         noise_fn = kwargs.get("noise_fn")       # tests: replaces the device generator (the reference run's CPU noise sequence)
         _warn_batch(conditioning, batch_size)
         self.make_schedule(S, ddim_eta=eta, verbose=verbose)
-        dev = self.model.device
-        C, H, W = shape
-        size = (batch_size, C, H, W)
-        img = torch.randn(size, device=dev) if x_T is None else x_T.to(dev, torch.float32).contiguous()
+        img, size = _start(self.model, batch_size, shape, x_T)
         tb = self.tables
-        return self._steps(img, size, np.flip(tb.timesteps), (tb.alphas, tb.alphas_prev, tb.sigmas, tb.sqrt_one_minus_alphas),
+        return _ddim_steps(self.model, img, size, np.flip(tb.timesteps), (tb.alphas, tb.alphas_prev, tb.sigmas, tb.sqrt_one_minus_alphas),
                            conditioning, unconditional_guidance_scale, unconditional_conditioning, noise_fn=noise_fn,
                            temperature=temperature, noise_dropout=noise_dropout, score_corrector=score_corrector,
                            corrector_kwargs=corrector_kwargs, classifier=classifier, origin_cond=origin_cond,
                            classifier_guide_scale=classifier_guide_scale, callback=callback, img_callback=img_callback,
                            log_every_t=log_every_t, paint=_Inpaint(self.model, mask, x0, size, kwargs.get("q_noise_fn")))
 
-    def _steps(self, img, size, steps, tables, conditioning, unconditional_guidance_scale, unconditional_conditioning, noise_fn=None,
-               temperature=1.0, noise_dropout=0.0, score_corrector=None, corrector_kwargs=None, classifier=None, origin_cond=None,
-               classifier_guide_scale=0.0, callback=None, img_callback=None, log_every_t=100, paint=None):
-        """The DDIM step loop (ddim.py:179-229 with p_sample_ddim :231-273): ``steps`` are the timestep values in visiting order,
-        ``tables`` = (alphas, alphas_prev, sigmas, sqrt_one_minus_alphas) indexed by len(steps) - 1 - i at step i.  sample() walks the
-        whole DDIM schedule, decode() a prefix of it (or of the original steps): one loop for both."""
-        dev = self.model.device
-        batch_size = size[0]
-        alphas, alphas_prev, sigmas, sqrt_one_minus_alphas = tables
-        total = steps.shape[0]
-        eps_fn = _Guided(self.model, conditioning, unconditional_guidance_scale, unconditional_conditioning, steps, size)
-        t_all = torch.tensor(steps.copy(), dtype=torch.float32, device=dev)[:, None].expand(total, batch_size).contiguous()
-        t_long = t_all.long() if score_corrector is not None else None     # the reference hands the callback `ts` (int64, ddim.py:217)
-        inter = {"x_inter": [img], "pred_x0": [img]}
-        for i in range(total):
-            index = total - i - 1
-            if paint is not None and paint.on:      # ddim.py:206-209
-                img = paint.blend(img, steps[i])
-            a_t, a_prev = alphas[index], alphas_prev[index]
-            if classifier is None:
-                e_t = eps_fn(img, t_all[i], i)
-            else:                            # ddim.py:374-380: the classifier gradient first ...
-                e_t, g = _eps_and_classifier_grad(self.model, classifier, lambda: eps_fn(img, t_all[i], i), img, t_all[i], origin_cond)
-                e_t = E.lincomb([(1.0, e_t), (-np.sqrt(np.float32(1.0) - a_t) * classifier_guide_scale, g)])
-            if score_corrector is not None:  # ... then the caller's callback on the guided eps (ddim.py:249-251, 382-384)
-                e_t = score_corrector.modify_score(self.model, e_t, img, t_long[i], conditioning, **(corrector_kwargs or {}))
-                e_t = E._dev_f32(e_t, dev)
-                eps_fn.reclaim_context()
-            sigma = sigmas[index]
-            noise = None
-            if sigma != 0.0:         # ddim.py:269-271: noise * temperature, then dropout of the noise (functional default: training)
-                noise = (noise_fn(size) if noise_fn is not None else torch.randn(size, device=dev)) * temperature
-                if noise_dropout > 0.0:
-                    noise = torch.nn.functional.dropout(noise, p=float(noise_dropout))
-                noise = noise.to(dev, torch.float32).contiguous()
-            img, pred_x0 = E.ddim_update(img, e_t, a_t, a_prev, sigma, sqrt_one_minus_alphas[index], noise)
-            if callback:
-                callback(i)
-            if img_callback:
-                img_callback(pred_x0, i)
-            if index % log_every_t == 0 or index == total - 1:
-                inter["x_inter"].append(img)
-                inter["pred_x0"].append(pred_x0)
-        return img, inter
-
-    def sample_with_classifier(self, S, batch_size, shape, conditioning=None, origin_cond=None, callback=None, normals_sequence=None,
-                               img_callback=None, quantize_x0=False, eta=0.0, mask=None, x0=None, temperature=1.0, noise_dropout=0.0,
-                               score_corrector=None, corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100,
-                               unconditional_guidance_scale=1.0, unconditional_conditioning=None, classifier=None,
-                               classifier_guide_scale=0.0, **kwargs):
-        return self.sample(S, batch_size, shape, conditioning, callback=callback, normals_sequence=normals_sequence,
-                           img_callback=img_callback, quantize_x0=quantize_x0, eta=eta, mask=mask, x0=x0, temperature=temperature,
-                           noise_dropout=noise_dropout, score_corrector=score_corrector, corrector_kwargs=corrector_kwargs,
-                           verbose=verbose, x_T=x_T, log_every_t=log_every_t, unconditional_guidance_scale=unconditional_guidance_scale,
-                           unconditional_conditioning=unconditional_conditioning, classifier=classifier, origin_cond=origin_cond,
-                           classifier_guide_scale=classifier_guide_scale, **kwargs)
+    sample_with_classifier = sample_with_classifier
 
 
 class PLMSSampler(object):
@@ -359,35 +383,14 @@ class PLMSSampler(object):
         reject_unsupported("PLMSSampler", dict(kwargs, quantize_x0=quantize_x0, temperature=temperature), dict(temperature=1.0))
         _warn_batch(conditioning, batch_size)
         tb = DDIMTables(self.model.alphas_cumprod, S, 0.0)
-        dev = self.model.device
-        C, H, W = shape
-        size = (batch_size, C, H, W)
-        img = torch.randn(size, device=dev) if x_T is None else x_T.to(dev, torch.float32).contiguous()
+        img, size = _start(self.model, batch_size, shape, x_T)
         steps = np.flip(tb.timesteps)
-        total = steps.shape[0]
-        guided = _Guided(self.model, conditioning, unconditional_guidance_scale, unconditional_conditioning, steps, size)
-        t_all = torch.tensor(steps.copy(), dtype=torch.float32, device=dev)[:, None].expand(total, batch_size).contiguous()
-        t_long = t_all.long() if score_corrector is not None else None     # the reference's `ts` / `ts_next` are int64 (plms.py:140-142)
-
-        def eps_fn(x, k):                    # get_model_output (plms.py:178-190): guided eps, then the caller's score corrector
-            e = guided(x, t_all[k], k)
-            if score_corrector is not None:
-                e = E._dev_f32(score_corrector.modify_score(self.model, e, x, t_long[k], conditioning, **(corrector_kwargs or {})), dev)
-                guided.reclaim_context()
-            return e
-        inter = {"x_inter": [img], "pred_x0": [img]}
         old_eps = []
-        paint = _Inpaint(self.model, mask, x0, size, kwargs.get("q_noise_fn"))
-        for i in range(total):
-            index = total - i - 1
-            if paint.on:                     # plms.py:147-150
-                img = paint.blend(img, steps[i])
-            upd = lambda x, e: E.ddim_update(x, e, tb.alphas[index], tb.alphas_prev[index], 0.0,
-                                             tb.sqrt_one_minus_alphas[index], None)
-            e_t = eps_fn(img, i)
+
+        def combine(e_t, i, eps_at, update):      # Adams-Bashforth over the eps history (plms.py:219-236)
             if len(old_eps) == 0:          # pseudo improved Euler (plms.py:219-223)
-                x_prev, _ = upd(img, e_t)
-                e_next = eps_fn(x_prev, min(i + 1, total - 1))
+                x_prev, _ = update(e_t)
+                e_next = eps_at(x_prev, min(i + 1, steps.shape[0] - 1))
                 e_p = E.lincomb([(0.5, e_t), (0.5, e_next)])
             elif len(old_eps) == 1:
                 e_p = E.lincomb([(1.5, e_t), (-0.5, old_eps[-1])])
@@ -395,99 +398,14 @@ class PLMSSampler(object):
                 e_p = E.lincomb([(23 / 12, e_t), (-16 / 12, old_eps[-1]), (5 / 12, old_eps[-2])])
             else:
                 e_p = E.lincomb([(55 / 24, e_t), (-59 / 24, old_eps[-1]), (37 / 24, old_eps[-2]), (-9 / 24, old_eps[-3])])
-            img, pred_x0 = upd(img, e_p)
             old_eps.append(e_t)
             if len(old_eps) >= 4:
                 old_eps.pop(0)
-            if callback:
-                callback(i)
-            if img_callback:
-                img_callback(pred_x0, i)
-            if index % log_every_t == 0 or index == total - 1:
-                inter["x_inter"].append(img)
-                inter["pred_x0"].append(pred_x0)
-        return img, inter
-
-
-class DPMSolverSampler(object):
-    """DPM-Solver++(2M): multistep, order 2, time_uniform, predict_x0, lower_order_final (only if S < 15)."""
-
-    def __init__(self, model, **kwargs):
-        self.model = model
-
-    @torch.no_grad()
-    def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None,
-               quantize_x0=False, eta=0.0, mask=None, x0=None, temperature=1.0, noise_dropout=0.0, score_corrector=None,
-               corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, unconditional_guidance_scale=1.0,
-               unconditional_conditioning=None, classifier=None, origin_cond=None, classifier_guide_scale=0.0, **kwargs):
-        # the reference's parameters in the reference's order (sampler.py:25-48), then the three of sample_with_classifier.  The
-        # reference ignores eta / temperature / noise_dropout, the callbacks and log_every_t here (sampler.py:24-56 passes none of
-        # them to DPM_Solver): same
-        reject_unsupported("DPMSolverSampler", dict(kwargs, quantize_x0=quantize_x0, mask=mask, x0=x0, score_corrector=score_corrector),
-                           dict(mask=None, x0=None, score_corrector=None))   # sampler.py:24-56 accepts and drops them
-        if S < 2:
-            raise AssertionError("DPM-Solver++(2M) needs steps >= order = 2 (dpm_solver.py:1083 asserts steps >= order)")
-        _warn_batch(conditioning, batch_size)
-        dev = self.model.device
-        C, H, W = shape
-        size = (batch_size, C, H, W)
-        x = torch.randn(size, device=dev) if x_T is None else x_T.to(dev, torch.float32).contiguous()
-        ns = DPMTables(self.model.alphas_cumprod)
-        ts = ns.time_steps(S)
-        t_model = [ns.model_time(t) for t in ts]
-        eps_fn = _Guided(self.model, conditioning, unconditional_guidance_scale, unconditional_conditioning, t_model[:S], size)
-        t_in_all = torch.tensor(t_model, dtype=torch.float32, device=dev)[:, None].expand(S + 1, batch_size).contiguous()
-
-        def model_fn(x, k):          # data prediction x0 = (x - sigma*eps)/alpha   (dpm_solver.py:386-393)
-            t = ts[k]
-            if classifier is None or not eps_fn.cfg:
-                noise = eps_fn(x, t_in_all[k], k)
-            else:                                          # double guidance (dpm_solver.py:1377-1393)
-                noise, g = _eps_and_classifier_grad(self.model, classifier, lambda: eps_fn(x, t_in_all[k], k), x, t_in_all[k], origin_cond)
-                noise = E.lincomb([(1.0, noise), (-classifier_guide_scale * ns.sigma(t), g)])
-            a, s = ns.alpha(t), ns.sigma(t)
-            return E.lincomb([(1.0 / a, x), (-s / a, noise)])
-
-        def first_update(x, s, t, m_s):
-            h = ns.lam(t) - ns.lam(s)
-            return E.lincomb([(ns.sigma(t) / ns.sigma(s), x), (-ns.alpha(t) * np.expm1(-h), m_s)])
-
-        def second_update(x, m1, m0, t1, t0, t):
-            l1, l0, lt = ns.lam(t1), ns.lam(t0), ns.lam(t)
-            h0, h = l0 - l1, lt - l0
-            r0 = h0 / h
-            k = ns.alpha(t) * (np.exp(-h) - np.float32(1.0))
-            # x_t = sig_t/sig_0 x - k m0 - 0.5 k (m0 - m1)/r0
-            return E.lincomb([(ns.sigma(t) / ns.sigma(t0), x), (-k - 0.5 * k / r0, m0), (0.5 * k / r0, m1)])
-
-        m_prev = [model_fn(x, 0)]
-        t_prev = [ts[0]]
-        x = first_update(x, ts[0], ts[1], m_prev[-1])
-        m_prev.append(model_fn(x, 1))
-        t_prev.append(ts[1])
-        for step in range(2, S + 1):
-            order = min(2, S + 1 - step) if S < 15 else 2
-            if order == 1:
-                x = first_update(x, t_prev[-1], ts[step], m_prev[-1])
-            else:
-                x = second_update(x, m_prev[0], m_prev[1], t_prev[0], t_prev[1], ts[step])
-            t_prev[0], m_prev[0] = t_prev[1], m_prev[1]
-            t_prev[1] = ts[step]
-            if step < S:
-                m_prev[1] = model_fn(x, step)
-        return x, None
-
-    def sample_with_classifier(self, S, batch_size, shape, conditioning=None, origin_cond=None, callback=None, normals_sequence=None,
-                               img_callback=None, quantize_x0=False, eta=0.0, mask=None, x0=None, temperature=1.0, noise_dropout=0.0,
-                               score_corrector=None, corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100,
-                               unconditional_guidance_scale=1.0, unconditional_conditioning=None, classifier=None,
-                               classifier_guide_scale=0.0, **kwargs):
-        return self.sample(S, batch_size, shape, conditioning, callback=callback, normals_sequence=normals_sequence,
-                           img_callback=img_callback, quantize_x0=quantize_x0, eta=eta, mask=mask, x0=x0, temperature=temperature,
-                           noise_dropout=noise_dropout, score_corrector=score_corrector, corrector_kwargs=corrector_kwargs,
-                           verbose=verbose, x_T=x_T, log_every_t=log_every_t, unconditional_guidance_scale=unconditional_guidance_scale,
-                           unconditional_conditioning=unconditional_conditioning, classifier=classifier, origin_cond=origin_cond,
-                           classifier_guide_scale=classifier_guide_scale, **kwargs)
+            return e_p
+        return _ddim_steps(self.model, img, size, steps, (tb.alphas, tb.alphas_prev, tb.sigmas, tb.sqrt_one_minus_alphas), conditioning,
+                           unconditional_guidance_scale, unconditional_conditioning, score_corrector=score_corrector,
+                           corrector_kwargs=corrector_kwargs, callback=callback, img_callback=img_callback, log_every_t=log_every_t,
+                           paint=_Inpaint(self.model, mask, x0, size, kwargs.get("q_noise_fn")), combine=combine)
 
 
 @torch.no_grad()

@@ -7,8 +7,7 @@ tests/golden/make_golden_g18.py).
       tried times and the final latent agree to 1e-4 relative (fp32 on both sides; the maker keeps every E at least 0.02 from 1);
   (d) the adaptive solver on the tiny UNet, fast route: it terminates at t_0 and the final latent is within TRAJ[prec] + d_ref, d_ref
       being the reference's own sensitivity to its step sequence.  No assertion on the number of evaluations;
-  *   the fast route with multistep / order 2 / time_uniform / predict_x0 is bit-equal to DPMSolverSampler.sample: the same launches
-      with the same coefficients;
+  *   DPMSolverSampler.sample is the fast route with multistep / order 2 / time_uniform / predict_x0: bit-equal latents;
   *   the generic route around ``lambda x, t, c: m.apply_model(x, t, c)`` agrees with the fast route within FWD[prec] per evaluation;
   *   guidance_type='classifier' through AlignmentClassifier.log_prob_grad and the x_start / v conversions equal their expressions."""
 import numpy as np
@@ -114,16 +113,19 @@ def test_fixed_step_latents_against_the_reference(prec, tag_p, monkeypatch):
 
 
 def test_fast_route_2m_is_bit_equal_to_the_dpm_solver_sampler(prec):
-    from diff_foley_amd import samplers as S
+    """DPMSolverSampler.sample builds the model's DPM_Solver and asks for DPM-Solver++(2M): the latents of that call and of the
+    solver asked directly for multistep / order 2 / time_uniform are the same bits, so the sampler selects that configuration
+    (lower_order_final included: 6 and 15 steps are its two sides) and adds nothing to it."""
+    import diff_foley_amd as P
     m = _tiny(prec)
     x, c, uc = _inputs(m)
     for steps in (6, 15):          # lower_order_final lowers the last step below 15 only
-        old, _ = S.DPMSolverSampler(m).sample(steps, B, SHAPE, c, unconditional_guidance_scale=SCALE, unconditional_conditioning=uc,
+        old, _ = P.DPMSolverSampler(m).sample(steps, B, SHAPE, c, unconditional_guidance_scale=SCALE, unconditional_conditioning=uc,
                                               x_T=x.clone())
         new = m.dpm_solver(c, SCALE, uc).sample(x.clone(), steps=steps, order=2, method="multistep", skip_type="time_uniform")
         assert torch.equal(old, new), (steps, rel_l2(new.cpu(), old.cpu()))
     # ... and without guidance (scale 1: the conditional evaluation alone)
-    old, _ = S.DPMSolverSampler(m).sample(6, B, SHAPE, c, x_T=x.clone())
+    old, _ = P.DPMSolverSampler(m).sample(6, B, SHAPE, c, x_T=x.clone())
     new = m.dpm_solver(c).sample(x.clone(), steps=6, order=2, method="multistep", skip_type="time_uniform")
     assert torch.equal(old, new)
 

@@ -16,7 +16,7 @@ from diff_foley_amd import samplers as S
 from helpers import GOLD
 
 COUNTERPART = {"LatentDiffusion": P.LatentDiffusion, "DDIMSampler": S.DDIMSampler, "PLMSSampler": S.PLMSSampler,
-               "DPMSolverSampler": S.DPMSolverSampler, "CAVP_Inference": P.CAVPInference}
+               "DPMSolverSampler": P.DPMSolverSampler, "CAVP_Inference": P.CAVPInference}
 
 # Deviations, each with its reason: {entry point: {parameter: reason}}.  A parameter listed here is exempt from the name / order /
 # default comparison.  A parameter the reference uses and the product silently ignores may NOT be listed: that is a wrong result, not
@@ -61,6 +61,11 @@ def compare(ref, got, deviations=(), extras=None):
 def test_the_fixture_names_every_entry_point():
     assert sorted(REFERENCE) == sorted(ENTRY_POINTS)
     assert set(DEVIATIONS) <= set(ENTRY_POINTS) and set(EXTRAS) <= set(ENTRY_POINTS)
+
+
+def test_the_moved_sampler_keeps_its_earlier_spelling():
+    from diff_foley_amd import dpm_solver
+    assert S.DPMSolverSampler is P.DPMSolverSampler is dpm_solver.DPMSolverSampler
 
 
 @pytest.mark.parametrize("point", ENTRY_POINTS)

@@ -1,6 +1,5 @@
 #!/usr/bin/env python
-"""Measure DPM_Solver.sample on the GPU for each method of the family, and the fast route's DPM-Solver++(2M) configuration beside
-DPMSolverSampler.sample on the same build.
+"""Measure DPM_Solver.sample on the GPU for each method of the family, and DPM-Solver++(2M) as DPMSolverSampler.sample selects it.
 
     python tools/dpm_family_bench.py [--precision fp16] [--batch 4] [--iters 10] [--steps2m 50] [--out profiles/dpm_family_bench_fp16.txt]
 
@@ -12,8 +11,8 @@ figure).  Every subject is LatentDiffusion.dpm_solver(...).sample(...) on the fa
                per second ("steps/s"), and the ms outside the UNet: the median minus evaluations x the median of one guided evaluation
                with a hoisted time embedding, measured alone in the same process.  For 'adaptive' the evaluation count is the run's own
                and the embedding is computed in the step, so its UNet figure is the in-step evaluation's.
-  2M           DPM_Solver(multistep, order 2, time_uniform, predict_x0) and DPMSolverSampler.sample at --steps2m, the old path
-               measured twice: the ratio new / old beside the spread of the two old runs.
+  2M           DPMSolverSampler.sample at --steps2m: DPM_Solver(multistep, order 2, time_uniform, predict_x0) behind the samplers'
+               call surface, with the start latent and the solver built inside the figure.
 
 Prints one JSON line per measurement; nothing is asserted.  Needs the GPU."""
 import argparse
@@ -30,7 +29,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import diff_foley_amd as P  # noqa: E402
-from diff_foley_amd import dpm_solver as D, samplers as S, synth  # noqa: E402
+from diff_foley_amd import dpm_solver as D, synth  # noqa: E402
 
 METHODS = {
     "singlestep order 3, 15 evaluations, time_uniform": dict(steps=15, order=3, method="singlestep", skip_type="time_uniform"),
@@ -113,19 +112,13 @@ def main():
              iters=a.iters)
     D._FastSession.__call__ = plain
 
-    # the 2M configuration beside the sampler that hard-codes it
+    # the 2M configuration, through the sampler that selects it
     St = a.steps2m
-    old = lambda: S.DPMSolverSampler(m).sample(St, B, (4, 16, 64), c, unconditional_guidance_scale=scale, unconditional_conditioning=uc, x_T=x)
-    sol = m.dpm_solver(c, scale, uc)
-    new = lambda: sol.sample(x, steps=St, order=2, method="multistep", skip_type="time_uniform")
-    equal = bool(torch.equal(old()[0], new()))
-    old1 = statistics.median(ev_ms(old, a.iters))
-    new1 = statistics.median(ev_ms(new, a.iters))
-    old2 = statistics.median(ev_ms(old, a.iters))
-    emit(what="2M", precision=m.engine.precision, B=B, steps=St, bit_equal=equal, ms_sampler_run1=round(old1, 3), ms_sampler_run2=round(old2, 3),
-         ms_dpm_solver=round(new1, 3), steps_per_s_sampler=round(1000.0 * St / min(old1, old2), 1),
-         steps_per_s_dpm_solver=round(1000.0 * St / new1, 1), ratio_new_over_old=round(new1 / (0.5 * (old1 + old2)), 4),
-         spread_of_old_runs=round(abs(old1 - old2) / (0.5 * (old1 + old2)), 4))
+    run2m = lambda: P.DPMSolverSampler(m).sample(St, B, (4, 16, 64), c, unconditional_guidance_scale=scale, unconditional_conditioning=uc, x_T=x)
+    ts = ev_ms(run2m, a.iters)
+    med = statistics.median(ts)
+    emit(what="2M", precision=m.engine.precision, B=B, steps=St, ms_median=round(med, 3), ms_min=round(min(ts), 3), ms_max=round(max(ts), 3),
+         steps_per_s=round(1000.0 * St / med, 1), iters=a.iters)
     if a.out:
         with open(a.out if os.path.isabs(a.out) else os.path.join(ROOT, a.out), "w") as f:
             f.write("\n".join(lines) + "\n")
