@@ -10,6 +10,7 @@ from . import engine  # noqa: F401
 from .ldm import (LatentDiffusion, AlignmentClassifier, AlignmentClassifierMetric, CAVPInference,  # noqa: F401
                   DiagonalGaussianDistribution, instantiate_from_config)
 from .samplers import DDIMSampler, PLMSSampler  # noqa: F401
+from .windows import WindowedConditioning  # noqa: F401
 from . import dpm_solver  # noqa: F401
 from .dpm_solver import DPMSolverSampler, NoiseScheduleVP, DPM_Solver, model_wrapper, model_wrapper_with_classifier  # noqa: F401
 from .video import ExtractCAVPFeatures, frames_to_tensor  # noqa: F401

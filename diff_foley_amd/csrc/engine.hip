@@ -732,6 +732,31 @@ int df_dpm_adaptive_error(const float* x_hi, const float* x_lo, const float* x_p
     HIPCHK(launch_dpm_adaptive_error(x_hi, x_lo, x_prev, norm, out, B, (long)n, atol, rtol, (hipStream_t)stream));
   });
 }
+// The geometry of df_window_gather / df_window_blend, checked on the host before anything is launched -> its device tables
+static WindowTables window_geometry(const char* what, const int32_t* starts, int K, int B, int64_t rows, int Ww, int W) {
+  need_positive(what, {{"batch", B}, {"windows", K}, {"window width", Ww}, {"total width", W}});
+  if (rows < 1) fail("%s: %ld rows per sample (at least 1)", what, (long)rows);
+  if (!starts) fail("%s: null pointer argument", what);
+  const char* why = nullptr;
+  if (!window_geometry_ok(starts, K, Ww, W, &why)) fail("%s: %d windows of %d columns over %d columns: %s", what, K, Ww, W, why);
+  WindowTables t;
+  HIPCHK(window_tables(starts, K, Ww, W, &t));
+  return t;
+}
+int df_window_gather(const float* x, float* win, const int32_t* starts, int K, int B, int64_t rows, int Ww, int W, void* stream) {
+  return guard([&] {
+    const WindowTables t = window_geometry("window_gather", starts, K, B, rows, Ww, W);
+    if (!x || !win) fail("window_gather: null pointer argument");
+    HIPCHK(launch_window_gather(x, win, t, B, K, (long)rows, Ww, W, (hipStream_t)stream));
+  });
+}
+int df_window_blend(const float* win, float* out, const int32_t* starts, int K, int B, int64_t rows, int Ww, int W, void* stream) {
+  return guard([&] {
+    const WindowTables t = window_geometry("window_blend", starts, K, B, rows, Ww, W);
+    if (!win || !out) fail("window_blend: null pointer argument");
+    HIPCHK(launch_window_blend(win, out, t, B, K, (long)rows, Ww, W, (hipStream_t)stream));
+  });
+}
 int df_ddim_update(const float* x, const float* e, const float* noise, float* x_prev, float* pred_x0, int64_t n,
                    float a_t, float a_prev, float sigma_t, float sqrt_one_minus_at, void* stream) {
   return guard([&] {

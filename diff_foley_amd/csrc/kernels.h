@@ -103,6 +103,24 @@ hipError_t launch_dpm_data_prediction(const float* x, const float* eps, float* o
 // launches, fixed summation order, no atomics (dpm.hip)
 hipError_t launch_dpm_adaptive_error(const float* x_hi, const float* x_lo, const float* x_prev, float* norm, float* out, int B, long n,
                                      float atol, float rtol, hipStream_t s);
+// ---- overlapped windows of a long fp32 tensor [B][rows][W] (windows.hip) ---------------------------------------
+// Device tables of one geometry: K windows of Ww columns at starts[k] over W columns; per column the first covering window, the number
+// of covering windows and fp32(1 / sum of the tent weights w(j) = min(j + 1, Ww - j))
+struct WindowTables {
+  const int* starts;
+  const int* k_first;
+  const int* k_count;
+  const float* inv_n;
+};
+// starts ascend, lie in [0, W - Ww] and leave no column uncovered; *why (may be NULL) names the first rule broken
+bool window_geometry_ok(const int* starts_host, int K, int Ww, int W, const char** why);
+// The tables of a geometry on the current device: built on the host and uploaded (blocking) the first time it is seen, then cached
+hipError_t window_tables(const int* starts_host, int K, int Ww, int W, WindowTables* out);
+// win[b * K + k][row][j] = x[b][row][starts[k] + j]: a copy
+hipError_t launch_window_gather(const float* x, float* win, const WindowTables& t, int B, int K, long rows, int Ww, int W, hipStream_t s);
+// out[b][row][x] = (sum over the covering k, ascending, of w(x - starts[k]) * win[b * K + k][row][x - starts[k]]) * inv_n[x]; one fma
+// per window, no atomics
+hipError_t launch_window_blend(const float* win, float* out, const WindowTables& t, int B, int K, long rows, int Ww, int W, hipStream_t s);
 
 // Row softmax: fp32 scores [rows][T] -> bf16 probabilities [rows][T]  (VAE single-head attention)
 // p rows have ldp >= T elements; columns [T, ldp) are written as zeros (the K padding of the P V GEMM)

@@ -37,6 +37,7 @@ import torch
 from . import engine as E
 from . import samplers
 from .schedule import ContinuousTables, DPMTables
+from .windows import WindowedConditioning
 
 F = np.float32
 
@@ -140,6 +141,12 @@ class _WrappedModel:
         self.fast_model = _ldm_of(model)
         self.fast = (self.fast_model is not None and model_type == "noise" and not self.model_kwargs and condition is not None
                      and guidance_type in ("classifier-free", "double-guide"))
+        if isinstance(condition, WindowedConditioning):      # a clip longer than one window (windows.py)
+            if not self.fast:
+                raise NotImplementedError("a windowed conditioning is served by the fast route only (LatentDiffusion.dpm_solver, or "
+                                          "model_wrapper around LatentDiffusion.apply_model with model_type='noise' and classifier-free "
+                                          "guidance): the generic route hands the condition to a callable that knows nothing of windows")
+            samplers.refuse_windowed_classifier(condition, classifier if guidance_type == "double-guide" else None)
 
     @property
     def cfg(self):

@@ -168,6 +168,8 @@ _SIGS = {
     "df_diffusion_loss": [C.c_void_p] * 7 + [C.c_int, C.c_int64, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p],
     "df_dpm_data_prediction": [C.c_void_p] * 4 + [C.c_int, C.c_int64, C.c_float, C.c_float, C.c_int, C.c_float, C.c_void_p],
     "df_dpm_adaptive_error": [C.c_void_p] * 5 + [C.c_int, C.c_int64, C.c_float, C.c_float, C.c_void_p],
+    "df_window_gather": [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p],
+    "df_window_blend": [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p],
     "df_ddim_update": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float,
                        C.c_float, C.c_float, C.c_void_p],
     "df_plan_count": [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
@@ -942,6 +944,41 @@ def lincomb(terms, out=None):
     ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in ts])
     coefs = (C.c_float * n)(*[float(c) for c, _ in terms])
     _chk(lib().df_lincomb(_ptr(out), ptrs, coefs, n, out.numel(), _stream()))
+    return out
+
+
+def _window_args(what, x, starts):
+    """(x as fp32 NCHW on its device, the int32 host array of the window starts, K)."""
+    if not x.is_cuda:
+        raise RuntimeError(f"{what}: the tensor must live on the GPU (there is no CPU path)")
+    x = _dev_f32(x, x.device)
+    if x.ndim != 4:
+        raise RuntimeError(f"{what}: expected a 4-D NCHW tensor, got shape {tuple(x.shape)}")
+    starts = [int(s) for s in starts]
+    return x, (C.c_int32 * max(len(starts), 1))(*starts), len(starts)
+
+
+def window_gather(x, starts, width):
+    """x [B][C][H][W] -> [B * K][C][H][width], row b * K + k = x[b, :, :, starts[k] : starts[k] + width] (df_window_gather, a copy).
+    The geometry is checked by the C entry (every column covered, no window outside): a bad one raises RuntimeError, nothing runs."""
+    x, arr, K = _window_args("window_gather", x, starts)
+    B, Cc, H, W = x.shape
+    out = torch.empty(B * K, Cc, H, max(int(width), 0), device=x.device, dtype=torch.float32)
+    with torch.cuda.device(x.device):
+        _chk(lib().df_window_gather(_ptr(x), _ptr(out), arr, K, B, Cc * H, int(width), W, _stream()))
+    return out
+
+
+def window_blend(win, starts, W):
+    """win [B * K][C][H][Ww] -> [B][C][H][W]: the tent-weighted mean of the windows over every column (df_window_blend; weight
+    min(j + 1, Ww - j) of window column j, fp32 accumulation in ascending k, one multiply by fp32(1 / sum of weights))."""
+    win, arr, K = _window_args("window_blend", win, starts)
+    N, Cc, H, Ww = win.shape
+    if K < 1 or N % K:
+        raise RuntimeError(f"window_blend: {N} window rows are no multiple of {K} windows")
+    out = torch.empty(N // K, Cc, H, max(int(W), 0), device=win.device, dtype=torch.float32)
+    with torch.cuda.device(win.device):
+        _chk(lib().df_window_blend(_ptr(win), _ptr(out), arr, K, N // K, Cc * H, Ww, int(W), _stream()))
     return out
 
 

@@ -24,6 +24,7 @@ import torch
 from . import dpm_solver as D
 from . import engine as E
 from . import samplers as S
+from . import windows as W
 from .align_metric import (AlignmentClassifierMetric, _MetricBackboneFacade, _MetricCondFacade,  # noqa: F401
                            _MetricFirstStageFacade, align_acc_clip_name, align_acc_frames, align_acc_specs)
 from .cavp import CAVPInference
@@ -300,6 +301,25 @@ class LatentDiffusion(_EngineModel):
 
     @_locked
     @torch.no_grad()
+    def get_windowed_conditioning(self, video_feat, hop=16, size_len=64):
+        """The conditioning of a clip of T >= 32 CAVP frames, longer than the one 32-frame window the model was trained on (no
+        reference counterpart): K windows of 32 frames at a hop of ``hop`` frames, the last one flush right, each
+        encoded on its own with positions 0..31 -- one df_window_gather over the frames and ONE df_cond_encode over the B * K windows.
+        ``size_len`` is the latent width of one window.  Hand the result to a sampler with ``size_len=cond.size_len_total``; with
+        T == 32 it holds get_learned_conditioning's bits and samples exactly like it."""
+        eng = self._require()
+        if getattr(video_feat, "ndim", 0) != 3:
+            raise ValueError(f"get_windowed_conditioning: video_feat of shape {tuple(getattr(video_feat, 'shape', ()))}, expected (B, T, dim)")
+        B, T, D = (int(v) for v in video_feat.shape)
+        starts, _ = W.plan_windows(T, hop, size_len)
+        feats = E._dev_f32(video_feat, self.device)
+        if len(starts) > 1:      # frames are rows of D floats: windows of 32 * D "columns" at starts s_k * D
+            feats = E.window_gather(feats.reshape(B, 1, 1, T * D), [s * D for s in starts], W.FRAMES * D).reshape(-1, W.FRAMES, D)
+        c = eng.cond_encode(feats)
+        return W.WindowedConditioning(c.reshape(B, len(starts), W.FRAMES, c.shape[-1]), starts, hop, T, size_len)
+
+    @_locked
+    @torch.no_grad()
     def apply_model(self, x_noisy, t, cond, return_ids=False):
         eng = self._require()
         c = self._cond_tensor(cond)
@@ -325,6 +345,25 @@ class LatentDiffusion(_EngineModel):
             raise NotImplementedError("VQ code-book decoding is not on the path (AutoencoderKL first stage)")
         # any batch size: df_vae_decode slices batches above 16 samples itself (2 GiB operand addressing, include/df_engine.h)
         return self._require().vae_decode(z)
+
+    @_locked
+    @torch.no_grad()
+    def decode_first_stage_windowed(self, z, hop_cols=None, size_len=64):
+        """decode_first_stage of a latent wider than one window, by the construction the long latent was sampled with: windows of
+        ``size_len`` latent columns at a hop of ``hop_cols`` (default size_len / 2), the last one flush right, each decoded by
+        df_vae_decode, and the (B * K, out_ch, f H, f size_len) images blended with the integer tent over their f * size_len columns
+        into (B, out_ch, f H, f W).  A latent of exactly ``size_len`` columns is decode_first_stage, bit for bit."""
+        eng = self._require()
+        z = E._dev_f32(z, self.device)
+        if z.ndim != 4:
+            raise ValueError(f"decode_first_stage_windowed: z of shape {tuple(z.shape)}, expected [B][C][H][W]")
+        Wc = int(size_len)
+        starts = W.window_starts(z.shape[3], Wc, Wc // 2 if hop_cols is None else hop_cols)
+        if len(starts) == 1:
+            return eng.vae_decode(z)
+        f = 2 ** (len(self.vae_cfg["ch_mult"]) - 1)
+        img = eng.vae_decode(E.window_gather(z, starts, Wc))
+        return E.window_blend(img, [f * s for s in starts], f * int(z.shape[3]))
 
     @_locked
     @torch.no_grad()
@@ -358,7 +397,7 @@ class LatentDiffusion(_EngineModel):
         S.reject_unsupported("LatentDiffusion.sample", dict(quantize_denoised=quantize_denoised), dict(quantize_denoised=False))
         if shape is None:
             shape = (batch_size, self.channels, self.image_size, self.image_size)
-        if cond is not None:
+        if cond is not None and not isinstance(cond, W.WindowedConditioning):
             cond = self._cond_tensor(cond)[:batch_size]
         # The reference hands p_sample_loop its named parameters only (ddpm.py:1264-1268): log_every_t, callback, img_callback and
         # start_T arriving in **kwargs have no effect there, and none here -- the intermediates follow self.log_every_t.  noise_fn and

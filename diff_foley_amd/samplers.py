@@ -16,6 +16,7 @@ import torch
 
 from . import engine as E
 from .schedule import DDIMTables, original_step_tables
+from .windows import WindowedConditioning
 
 import os as _os
 _NO_HOIST = bool(int(_os.environ.get("DF_NO_THOIST", "0")))      # A/B switch: time embedding inside every step
@@ -100,8 +101,13 @@ class _Guided:
         self.eng = model.engine
         self.cfg = not (uc is None or scale == 1.0)
         self.scale = float(scale)
-        cond = model._cond_tensor(cond)
-        self._ctx = torch.cat([model._cond_tensor(uc), cond]) if self.cfg else cond
+        self.win = None                  # a WindowedConditioning of more than one window: gather -> UNet -> blend per call
+        if isinstance(cond, WindowedConditioning):
+            cond, uc, size = self._windowed(cond, uc, size)
+        else:
+            cond = model._cond_tensor(cond)
+            uc = model._cond_tensor(uc)
+        self._ctx = torch.cat([uc, cond]) if self.cfg else cond
         self.eng.set_context(self._ctx)
         model._ctx_owner = None          # invalidate apply_model's cached context
         self.hoisted = False
@@ -115,6 +121,32 @@ class _Guided:
                     raise
                 self.hoisted = False
 
+    def _windowed(self, cond, uc, size):
+        """A WindowedConditioning (windows.py) -> (conditional rows, unconditional rows, the size the UNet sees).  One window is the
+        plain call on that window's conditioning: nothing is gathered or blended, the bits are the plain call's.  More than one: the
+        context rows of the window batch (row b * K + k), and ``size`` becomes (B * K, C, H, Wc) for the timestep table."""
+        if size is None:
+            raise ValueError("a windowed conditioning needs the size of the long latent")
+        cond.check_latent(size)
+        B, Cc, H, W = (int(v) for v in size)
+        c = cond.rows(B).to(self.m.device, torch.float32)
+        u = cond.uncond_rows(uc, B) if self.cfg else None
+        if cond.K > 1:
+            self.win = cond
+            self._long = (B, Cc, H, W)
+            size = (B * cond.K, Cc, H, cond.size_len)
+        return c, u, size
+
+    def _window_eval(self, fwd, x, t):
+        """eps on the long latent: cut the K windows out, evaluate them as ONE UNet batch (guidance included), blend them back."""
+        win = self.win
+        if tuple(x.shape) != self._long:
+            raise ValueError(f"windowed evaluation of a latent of shape {tuple(x.shape)}, the sample was opened for {self._long}")
+        if t.numel() == x.shape[0]:      # one timestep per sample -> one per window row (a broadcast copy; a single t serves all rows)
+            t = t.reshape(-1, 1).expand(x.shape[0], win.K).reshape(-1)
+        e = fwd(E.window_gather(x, win.col_starts, win.size_len), t)
+        return E.window_blend(e, win.col_starts, win.size_len_total)
+
     def reclaim_context(self):
         """A caller-supplied callback (score_corrector) may have evaluated the model itself -- ``model.apply_model`` and the
         ``model.model`` facades set THEIR context in the engine.  Put the sampler's [uncond ; cond] context back."""
@@ -124,8 +156,12 @@ class _Guided:
 
     def __call__(self, x, t, k=None):
         k = k if self.hoisted else None
-        fwd = (lambda kk: self.eng.unet_forward_cfg(x, t, self.scale, ts_index=kk)) if self.cfg else \
-              (lambda kk: self.eng.unet_forward(x, t, ts_index=kk))
+        unet = (lambda xx, tt, kk: self.eng.unet_forward_cfg(xx, tt, self.scale, ts_index=kk)) if self.cfg else \
+               (lambda xx, tt, kk: self.eng.unet_forward(xx, tt, ts_index=kk))
+        if self.win is None:
+            fwd = lambda kk: unet(x, t, kk)
+        else:
+            fwd = lambda kk: self._window_eval(lambda xx, tt: unet(xx, tt, kk), x, t)
         if k is None:
             return fwd(None)
         try:
@@ -140,6 +176,15 @@ class _Guided:
                           f"({ex}); the remaining steps compute the embedding inside the step", RuntimeWarning, stacklevel=2)
             self.hoisted = False
             return fwd(None)
+
+
+def refuse_windowed_classifier(cond, classifier):
+    """Double guidance over windows is not defined here: the classifier scores one 32-frame window, and whether its gradient on the
+    long latent is taken window by window and blended like eps, or on some other cover, is a modelling decision nobody has made."""
+    if classifier is not None and isinstance(cond, WindowedConditioning):
+        raise NotImplementedError("classifier guidance with a windowed conditioning is not supported: the alignment classifier scores "
+                                  "one 32-frame window, and how its gradient is to be combined over overlapping windows of a long "
+                                  "latent has not been decided; sample without the classifier, or one window at a time")
 
 
 def _classifier_grad(model, classifier, x, t, origin_cond):
@@ -202,6 +247,7 @@ def _ddim_steps(model, img, size, steps, tables, conditioning, unconditional_gui
     evaluation at step k, ``update(e)`` the step's df_ddim_update from the current latent."""
     dev = model.device
     batch_size = size[0]
+    refuse_windowed_classifier(conditioning, classifier)
     alphas, alphas_prev, sigmas, sqrt_one_minus_alphas = tables
     total = steps.shape[0]
     guided = _Guided(model, conditioning, unconditional_guidance_scale, unconditional_conditioning, steps, size)
@@ -417,7 +463,7 @@ def ancestral_sample(model, cond, shape, x_T=None, timesteps=None, log_every_t=N
     b = shape[0]
     T = model.num_timesteps if timesteps is None else timesteps
     log_every_t = log_every_t or model.log_every_t
-    eps_fn = _Guided(model, cond, 1.0, None)
+    eps_fn = _Guided(model, cond, 1.0, None, size=tuple(shape))
     tab = {k: getattr(model, k).cpu().numpy() for k in ("sqrt_recip_alphas_cumprod", "sqrt_recipm1_alphas_cumprod",
                                                         "posterior_mean_coef1", "posterior_mean_coef2",
                                                         "posterior_log_variance_clipped")}

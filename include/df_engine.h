@@ -328,6 +328,21 @@ int df_dpm_data_prediction(const float* x_dev, const float* eps_dev, float* out_
  * wavefront over the batch: no atomics, fixed summation order.  A NaN norm makes out NaN.  B, n >= 1.  Stateless. */
 int df_dpm_adaptive_error(const float* x_hi_dev, const float* x_lo_dev, const float* x_prev_dev, float* norm_dev, float* out_dev,
                           int B, int64_t n, float atol, float rtol, void* stream);
+/* Overlapped windows of a long fp32 tensor x [B][rows][W] (an NCHW latent or image with rows = C * H): K windows of Ww columns,
+ * window k at column starts[k] (HOST int32 array).  Both entries check the geometry on the host and launch nothing when it is bad
+ * (return 1, df_last_error names the rule): K, B, rows, Ww >= 1, W >= Ww, 0 <= starts[k], starts[k] + Ww <= W, starts ascending, every
+ * column of [0, W) covered by a window.  Any integer starts and widths are served (4-byte accesses only).
+ *   df_window_gather: win[b * K + k][row][j] = x[b][row][starts[k] + j], win [B * K][rows][Ww] -- a copy.
+ *   df_window_blend:  out[b][row][c] = (sum_k w(c - starts[k]) * win[b * K + k][row][c - starts[k]]) * inv_n[c] over the windows that
+ *     cover column c in ascending k, w(j) = min(j + 1, Ww - j) (an integer tent), inv_n[c] = fp32(1 / sum_k w(c - starts[k])) with the
+ *     reciprocal taken in double on the host.  fp32 accumulation from zero, one fma per window, one multiply: no atomics, no scatter,
+ *     equal inputs give equal bits.  out must not alias win.
+ * The per-column tables of a geometry are built on the host and uploaded with a blocking copy the first time the geometry is seen on a
+ * device, then reused (up to 64 geometries are kept).  Stateless otherwise, like df_lincomb. */
+int df_window_gather(const float* x_dev, float* win_dev, const int32_t* starts_host, int K, int B, int64_t rows, int Ww, int W,
+                     void* stream);
+int df_window_blend(const float* win_dev, float* out_dev, const int32_t* starts_host, int K, int B, int64_t rows, int Ww, int W,
+                    void* stream);
 /* DDIM update (ddim.py:258-272).  noise may be NULL (eta = 0). */
 int df_ddim_update(const float* x_dev, const float* e_dev, const float* noise_dev, float* x_prev_dev,
                    float* pred_x0_dev, int64_t n, float a_t, float a_prev, float sigma_t, float sqrt_one_minus_at,
